@@ -10,6 +10,15 @@ Launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 (single process, no torchrun, for N=1).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time exactly
+K steps, print the line.  `--full` adds the measurements that take runs of their
+own: the plain-DP reference arm (`vs_baseline`, `baseline_images_per_sec`) and one
+post-bracket step with loss readback (`final_loss`); without it those keys are null.
+`--dump-outputs DIR` writes what the last timed step computed (the updated flat
+parameters) as DIR/params.npy for build-to-build comparison; that step then starts
+from the seeded start state, so that its inputs are the same in every run (see
+StartState, dump_outputs).
 """
 from __future__ import annotations
 
@@ -29,6 +38,77 @@ os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
 os.environ.setdefault("TORCHINDUCTOR_CACHE_DIR", "/tmp/draco_inductor_cache")
 
 import torch
+
+DUMP_BUDGET_BYTES = 60 * 2**20  # stays under the 64 MB cap incl. .npy headers
+
+
+def _optimizer_state(tr):
+    return {name: getattr(tr.opt, name)
+            for name in ("buf", "exp_avg", "exp_avg_sq", "max_exp_avg_sq")
+            if isinstance(getattr(tr.opt, name, None), torch.Tensor)}
+
+
+class StartState:
+    """Seeded start state (flat parameters + optimizer state) for --dump-outputs.
+
+    Training is chaotic and GPU conv backward is not bitwise reproducible (see
+    VoteAggregator): measured on ResNet-18, a 1e-6 relative parameter perturbation
+    moves the NEXT step's gradient by ~5%, so after a few steps two runs of one
+    build hold unrelated gradients and nothing could be compared output for output.
+    With --dump-outputs the LAST timed step therefore starts from this snapshot
+    (two in-place device copies inside the bracket, once per run, ~0.1 ms): its
+    inputs — state, batch and adversary of step warmup+steps-1 — are then identical
+    from run to run, and its outputs differ only by that one step's fp-reorder
+    noise.  restore() puts the trained state back (minus the rewound step's update)
+    so post-bracket telemetry still sees a trained model."""
+
+    def __init__(self, tr):
+        self.live = [tr.space.flat_param, *_optimizer_state(tr).values()]
+        self.start = [t.clone() for t in self.live]
+        self.trained = None
+
+    def _load(self, src):
+        with torch.no_grad():
+            for dst, s in zip(self.live, src):
+                dst.copy_(s)
+
+    def rewind(self):
+        self.trained = [t.clone() for t in self.live]
+        self._load(self.start)
+
+    def restore(self):
+        if self.trained is not None:
+            self._load(self.trained)
+
+
+def dump_outputs(tr, out_dir):
+    """Write what a caller of the last train_step() holds afterwards — the updated
+    flat parameters — as float32 DIR/params.npy.  The step started from StartState
+    (zero optimizer buffers), so params = start - lr * update(decoded gradient):
+    the decoded gradient is in the dump at lr/|param| resolution (float32 keeps
+    ~5 of its digits at lr=0.01), while one bf16 step's own run-to-run noise
+    (MIOpen fwd+bwd: 0.6-1% of the gradient norm on identical inputs, 0.1% in
+    fp32) lands at ~5e-6 of the parameter norm.  The gradient and the optimizer
+    buffer themselves are NOT dumped: after the rewound step both are that same
+    gradient again, carrying that noise at full size.  An array over the byte
+    budget is written as a fixed seeded sample (sorted indices of randperm(d),
+    seed 0), so two builds run with the same arguments dump the same elements."""
+    import numpy as np
+
+    d = tr.space.d  # drop the shard-alignment padding
+    arrays = {"params": tr.space.flat_param}
+    share = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    idx = None
+    if d > share:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(d, generator=g)[:share].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach()[:d]
+        if idx is not None:
+            a = a[idx.to(a.device)]  # gather on device: only the sample crosses
+        a = a.to(device="cpu", dtype=torch.float32)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.contiguous().numpy())
 
 
 def main():
@@ -62,6 +142,12 @@ def main():
     # (BASELINE.json north star: "no Triton").  The flag documents the measured +27%
     # for anyone who wants it.
     p.add_argument("--compile", type=lambda v: v.lower() in ("1","true"), default=False)
+    p.add_argument("--full", action="store_true",
+                   help="also run the plain-DP reference arm (vs_baseline) and the "
+                        "post-bracket loss-readback step (final_loss)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write the last step's updated parameters "
+                        "as DIR/params.npy (float32, <= 64 MB)")
     args = p.parse_args()
 
     from draco_amd.config import Config
@@ -87,7 +173,7 @@ def main():
         max_steps=args.steps + args.warmup + 10,
         eval_freq=0,
         log_dir="",
-        train_dir="gpurun_out/bench_ckpt",
+        train_dir="output/bench_ckpt",
         topology="colocated",
         channels_last=args.channels_last,
         hip_graphs=args.hip_graphs,
@@ -98,9 +184,10 @@ def main():
     t.logger.close()
     on_gpu = t.device.type == "cuda"
 
-    def timed_region(tr, steps, warmup):
+    def timed_region(tr, steps, warmup, start_state=None):
         """warmup untimed, then EXACTLY `steps` steps bracketed by barrier+sync on
-        both sides; returns MAX elapsed over ranks (slowest rank defines the job)."""
+        both sides; returns MAX elapsed over ranks (slowest rank defines the job).
+        With a start_state the last step runs from it (see StartState)."""
         for _ in range(warmup):
             tr.train_step()
         # inside the timed region: no per-step host sync, no per-step loss readback
@@ -111,7 +198,9 @@ def main():
         if on_gpu:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            if start_state is not None and i == steps - 1:
+                start_state.rewind()
             tr.train_step()
         if on_gpu:
             torch.cuda.synchronize()
@@ -128,10 +217,15 @@ def main():
             elapsed = float(el_dev[0])
         return elapsed
 
-    elapsed = timed_region(t, args.steps, args.warmup)
+    start_state = StartState(t) if args.dump_outputs else None
+    elapsed = timed_region(t, args.steps, args.warmup, start_state)
+    if start_state is not None:
+        if rank == 0:
+            dump_outputs(t, args.dump_outputs)
+        start_state.restore()
 
-    # post-bracket honesty telemetry: one more step with loss readback
-    final_loss = t.train_step()["loss"]
+    # post-bracket honesty telemetry (--full): one more step with loss readback
+    final_loss = t.train_step()["loss"] if args.full else None
     ms_per_step = elapsed / args.steps * 1000.0
 
     # DISTINCT images per step (redundant compute is the price of the code and is
@@ -149,21 +243,21 @@ def main():
         distinct_per_step = world * args.batch_size
         processed = distinct_per_step
 
-    # ---- plain-DP reference arm: same model/world, approach=baseline mode=normal,
-    # NO adversary, processing the SAME distinct images per step as the coded arm
-    # (cyclic trains an n*B global batch, so the fair plain-DP rank batch is
+    # ---- plain-DP reference arm (--full only): same model/world, approach=baseline
+    # mode=normal, NO adversary, processing the SAME distinct images per step as the
+    # coded arm (cyclic trains an n*B global batch, so the fair plain-DP rank batch is
     # distinct/world) — vs_baseline = coded ÷ plain throughput at equal work.
     # (The reference repo publishes no numbers, BASELINE.md, so the plain arm is
     # the denominator.)
     vs_baseline = None
     baseline_ips = None
-    if args.approach != "baseline":
+    if args.full and args.approach != "baseline":
         import dataclasses
 
         bcfg = dataclasses.replace(
             cfg, approach="baseline", mode="normal", worker_fail=0, err_mode="none",
             batch_size=max(distinct_per_step // world, 1),
-            train_dir="gpurun_out/bench_ckpt_base")
+            train_dir="output/bench_ckpt_base")
         tb = Trainer(bcfg)
         tb.logger.stdout_every = 0
         tb.logger.close()
@@ -196,7 +290,8 @@ def main():
             # same box — the reference publishes no absolute numbers
             "vs_baseline": vs_baseline,
             "baseline_images_per_sec": round(baseline_ips, 2) if baseline_ips else None,
-            "final_loss": round(final_loss, 4) if final_loss == final_loss else None,
+            "final_loss": (round(final_loss, 4)
+                           if final_loss is not None and final_loss == final_loss else None),
             "skipped_updates": t.skipped_updates,
             "vote_degenerate_steps": getattr(t.agg, "degenerate_steps", None),
             "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 3) if on_gpu else None,

@@ -8,7 +8,7 @@
 # tools/diag_cfg5_isolate.py for the isolation matrix.
 N=${1:-8}
 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-    bench.py --gpus "$N" --steps "${STEPS:-20}" --warmup "${WARMUP:-6}" \
+    bench.py --full --gpus "$N" --steps "${STEPS:-20}" --warmup "${WARMUP:-6}" \
     --approach cyclic --mode cyclic --worker-fail 2 --err-mode rev_grad \
     --network ResNet50 --dataset ImageNetSynthetic --batch-size 32 --dtype bf16 \
     --compile false --channels-last false

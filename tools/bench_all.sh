@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 run () {
   name=$1; shift
-  timeout 500 python bench.py --steps 20 --warmup 5 "$@" \
+  timeout 500 python bench.py --full --steps 20 --warmup 5 "$@" \
     > "gpurun_out/bench_${name}.json" 2>"gpurun_out/bench_${name}.err"
   echo "== $name rc=$?"
   grep -o '{"metric".*}' "gpurun_out/bench_${name}.json" | \
