@@ -29,6 +29,11 @@ static inline int n_blocks(long work, int per_block) {
   TORCH_CHECK(t.is_cuda(), #t " must be on GPU"); \
   TORCH_CHECK(t.is_contiguous(), #t " must be contiguous")
 
+// index / segment-bound tensors: the kernels read them as 64-bit
+#define CHECK_IDX(t) \
+  CHECK_IN(t); \
+  TORCH_CHECK(t.scalar_type() == torch::kInt64, #t " must be int64")
+
 static inline hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
@@ -78,6 +83,7 @@ void fused_sgd_step(torch::Tensor param, torch::Tensor grad, torch::Tensor buf,
                     bool nesterov, bool first_step, torch::Tensor guard) {
   CHECK_IN(param); CHECK_IN(grad);
   TORCH_CHECK(param.numel() % 4 == 0, "flat param length must be a multiple of 4");
+  TORCH_CHECK(grad.numel() == param.numel(), "fused_sgd_step: grad must have param's length");
   long n4 = param.numel() / 4;
   int blocks = n_blocks(n4, NTHREADS);
   bool mom = momentum != 0.0;
@@ -90,7 +96,11 @@ void fused_sgd_step(torch::Tensor param, torch::Tensor grad, torch::Tensor buf,
     TORCH_CHECK(guard.is_cuda() && guard.scalar_type() == torch::kBool, "guard must be a GPU bool");
     gd = guard.data_ptr<bool>();
   }
-  if (mom) { CHECK_IN(buf); bb = (float4 *)buf.data_ptr<float>(); }
+  if (mom) {
+    CHECK_IN(buf);
+    TORCH_CHECK(buf.numel() == param.numel(), "fused_sgd_step: buf must have param's length");
+    bb = (float4 *)buf.data_ptr<float>();
+  }
   hipStream_t s = cur_stream();
   if (mom && nesterov)
     hipLaunchKernelGGL((k_sgd<true, true>), dim3(blocks), dim3(NTHREADS), 0, s,
@@ -109,7 +119,8 @@ template <bool AMS>
 __global__ void k_adam(float4 *__restrict__ p, const float4 *__restrict__ g,
                        float4 *__restrict__ m, float4 *__restrict__ v,
                        float4 *__restrict__ vmax, long n4, float lr_t, float beta1,
-                       float beta2, float eps, float wd,
+                       float beta2, float omb1 /* 1-beta1 */, float omb2 /* 1-beta2 */,
+                       float eps, float wd,
                        const bool *__restrict__ guard) {
   if (guard != nullptr && !*guard) return;  // nan-guard: whole update is a no-op
   long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -124,8 +135,8 @@ __global__ void k_adam(float4 *__restrict__ p, const float4 *__restrict__ g,
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (wd != 0.f) dg[c] = fmaf(wd, pp[c], dg[c]);
-      mm[c] = fmaf(beta1, mm[c], (1.f - beta1) * dg[c]);
-      ss[c] = fmaf(beta2, ss[c], (1.f - beta2) * dg[c] * dg[c]);
+      mm[c] = fmaf(beta1, mm[c], omb1 * dg[c]);
+      ss[c] = fmaf(beta2, ss[c], omb2 * dg[c] * dg[c]);
       dn[c] = ss[c];
     }
     if (AMS) {
@@ -149,11 +160,18 @@ void fused_adam_step(torch::Tensor param, torch::Tensor grad, torch::Tensor exp_
                      double lr, double beta1, double beta2, double eps,
                      double weight_decay, bool amsgrad, torch::Tensor guard) {
   CHECK_IN(param); CHECK_IN(grad); CHECK_IN(exp_avg); CHECK_IN(exp_avg_sq);
+  TORCH_CHECK(param.numel() % 4 == 0, "flat param length must be a multiple of 4");
+  TORCH_CHECK(grad.numel() == param.numel() && exp_avg.numel() == param.numel() &&
+                  exp_avg_sq.numel() == param.numel(),
+              "fused_adam_step: grad and state must have param's length");
   long n4 = param.numel() / 4;
   int blocks = n_blocks(n4, NTHREADS);
   double bc1 = 1.0 - pow(beta1, (double)step);
   double bc2 = 1.0 - pow(beta2, (double)step);
   float lr_t = (float)(lr * sqrt(bc2) / bc1);
+  // 1-beta is formed in double: in fp32, 1.f - 0.999f cancels to 1.3e-5 relative
+  // error, which lands undiminished in exp_avg_sq (the fallback uses the double too)
+  float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   hipStream_t s = cur_stream();
   auto pp = (float4 *)param.data_ptr<float>();
   auto gg = (const float4 *)grad.data_ptr<float>();
@@ -166,13 +184,16 @@ void fused_adam_step(torch::Tensor param, torch::Tensor grad, torch::Tensor exp_
   }
   if (amsgrad) {
     CHECK_IN(max_exp_avg_sq);
+    TORCH_CHECK(max_exp_avg_sq.numel() == param.numel(),
+                "fused_adam_step: max_exp_avg_sq must have param's length");
     hipLaunchKernelGGL((k_adam<true>), dim3(blocks), dim3(NTHREADS), 0, s, pp, gg, mm, vv,
                        (float4 *)max_exp_avg_sq.data_ptr<float>(), n4, lr_t,
-                       (float)beta1, (float)beta2, (float)eps, (float)weight_decay, gd);
+                       (float)beta1, (float)beta2, omb1, omb2, (float)eps,
+                       (float)weight_decay, gd);
   } else {
     hipLaunchKernelGGL((k_adam<false>), dim3(blocks), dim3(NTHREADS), 0, s, pp, gg, mm, vv,
-                       nullptr, n4, lr_t, (float)beta1, (float)beta2, (float)eps,
-                       (float)weight_decay, gd);
+                       nullptr, n4, lr_t, (float)beta1, (float)beta2, omb1, omb2,
+                       (float)eps, (float)weight_decay, gd);
   }
 }
 
@@ -196,6 +217,7 @@ void inject(torch::Tensor grad, std::string mode, bool cyclic) {
   if (mode == "rev_grad") { a = cyclic ? (1.f + ADV) : ADV; b = 0.f; }
   else if (mode == "constant") { a = cyclic ? 1.f : 0.f; b = ADV; }
   else TORCH_CHECK(false, "inject: unknown mode ", mode);
+  TORCH_CHECK(grad.numel() % 4 == 0, "inject: length must be a multiple of 4");
   long n4 = grad.numel() / 4;
   hipLaunchKernelGGL(k_axpb, dim3(n_blocks(n4, NTHREADS)), dim3(NTHREADS), 0, cur_stream(),
                      (float4 *)grad.data_ptr<float>(), n4, a, b);
@@ -225,8 +247,9 @@ __global__ void k_rows_equal(const float4 *__restrict__ x, const long *__restric
 
 torch::Tensor rows_equal(torch::Tensor x, torch::Tensor a_idx, torch::Tensor b_idx,
                          double atol) {
-  CHECK_IN(x); CHECK_IN(a_idx); CHECK_IN(b_idx);
+  CHECK_IN(x); CHECK_IDX(a_idx); CHECK_IDX(b_idx);
   TORCH_CHECK(x.dim() == 2, "rows_equal: x must be 2D");
+  TORCH_CHECK(a_idx.numel() == b_idx.numel(), "rows_equal: index lengths differ");
   long k = a_idx.numel();
   long d = x.size(1);
   TORCH_CHECK(d % 4 == 0, "rows_equal: row length must be a multiple of 4");
@@ -249,6 +272,16 @@ __device__ inline void atomic_max_f32(float *addr, float val) {
   atomicMax((int *)addr, __float_as_int(val));
 }
 
+// Non-finite rule of the four vote statistics: |v| with NaN canonicalised to +inf, so
+// any NaN/+-Inf element (Inf - Inf included) makes its cell exactly +inf.  fmaxf
+// alone DROPS a NaN operand, which would let a NaN-sending member compare equal to
+// everyone.  +inf (not NaN) because the statistic goes through a cross-rank MAX
+// allreduce next, and it is the largest value under the float-as-int atomicMax.
+__device__ inline float abs_nan_inf(float v) {
+  float a = fabsf(v);
+  return (a != a) ? INFINITY : a;
+}
+
 template <bool PAIR>
 __global__ void k_absmax(const float4 *__restrict__ x, const long *__restrict__ ai,
                          const long *__restrict__ bi, float *__restrict__ out, long d4,
@@ -258,15 +291,20 @@ __global__ void k_absmax(const float4 *__restrict__ x, const long *__restrict__ 
   const float4 *rb = PAIR ? (x + bi[row] * stride4) : nullptr;
   long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
   long stride = gridDim.x * (long)blockDim.x;
-  float mx = 0.f;
+  // |v| as its bit pattern orders like the float for every non-NaN value, and a NaN
+  // pattern sorts ABOVE +inf: the integer max keeps a NaN that fmaxf would drop, and
+  // one min against +inf's pattern then applies the non-finite rule per thread
+  int mi = 0;
   for (; i < d4; i += stride) {
     float4 a = ra[i];
     if (PAIR) {
       float4 b = rb[i];
       a = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
     }
-    mx = fmaxf(mx, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
+    mi = max(mi, max(max(__float_as_int(a.x) & 0x7fffffff, __float_as_int(a.y) & 0x7fffffff),
+                     max(__float_as_int(a.z) & 0x7fffffff, __float_as_int(a.w) & 0x7fffffff)));
   }
+  float mx = __int_as_float(min(mi, 0x7f800000));
 #pragma unroll
   for (int off = WAVE / 2; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off, WAVE));
   __shared__ float wmax[NTHREADS / WAVE];
@@ -281,8 +319,11 @@ __global__ void k_absmax(const float4 *__restrict__ x, const long *__restrict__ 
 }
 
 torch::Tensor pair_maxdiff(torch::Tensor x, torch::Tensor a_idx, torch::Tensor b_idx) {
-  CHECK_IN(x); CHECK_IN(a_idx); CHECK_IN(b_idx);
+  CHECK_IN(x); CHECK_IDX(a_idx); CHECK_IDX(b_idx);
+  TORCH_CHECK(x.dim() == 2, "pair_maxdiff: x must be 2D");
+  TORCH_CHECK(a_idx.numel() == b_idx.numel(), "pair_maxdiff: index lengths differ");
   long k = a_idx.numel(), d = x.size(1);
+  TORCH_CHECK(d % 4 == 0, "pair_maxdiff: row length must be a multiple of 4");
   auto out = torch::zeros({k}, torch::dtype(torch::kFloat32).device(x.device()));
   if (d == 0 || k == 0) return out;
   dim3 grid(n_blocks(d / 4 / 8, NTHREADS), (unsigned)k);
@@ -294,7 +335,9 @@ torch::Tensor pair_maxdiff(torch::Tensor x, torch::Tensor a_idx, torch::Tensor b
 
 torch::Tensor row_absmax(torch::Tensor x) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dim() == 2, "row_absmax: x must be 2D");
   long m = x.size(0), d = x.size(1);
+  TORCH_CHECK(d % 4 == 0, "row_absmax: row length must be a multiple of 4");
   auto out = torch::zeros({m}, torch::dtype(torch::kFloat32).device(x.device()));
   if (d == 0 || m == 0) return out;
   dim3 grid(n_blocks(d / 4 / 8, NTHREADS), (unsigned)m);
@@ -343,7 +386,7 @@ __global__ void k_seg_absmax(const float *__restrict__ x, const long *__restrict
         int mid = (lo + hi + 1) >> 1;
         if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
       }
-      v = fabsf(PAIR ? (ra[i] - rb[i]) : ra[i]);
+      v = abs_nan_inf(PAIR ? (ra[i] - rb[i]) : ra[i]);  // feeds both paths below
     }
     int lo0 = __shfl(lo, 0, WAVE);
     if (__all(valid && lo == lo0)) {
@@ -357,12 +400,12 @@ __global__ void k_seg_absmax(const float *__restrict__ x, const long *__restrict
   __syncthreads();
   for (int l = threadIdx.x; l < L; l += blockDim.x) {
     float m = __int_as_float(s_max[l]);
-    if (m > 0.f) atomic_max_f32(&out[r * L + l], m);
+    if (m > 0.f) atomic_max_f32(&out[r * L + l], m);  // +inf passes; NaN never gets here
   }
 }
 
 torch::Tensor segment_absmax(torch::Tensor x, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IN(seg);
+  CHECK_IN(x); CHECK_IDX(seg);
   long m = x.size(0), d = x.size(1);
   int L = (int)seg.numel() - 1;
   auto out = torch::zeros({m, L}, torch::dtype(torch::kFloat32).device(x.device()));
@@ -377,7 +420,9 @@ torch::Tensor segment_absmax(torch::Tensor x, torch::Tensor seg) {
 
 torch::Tensor segment_pair_maxdiff(torch::Tensor x, torch::Tensor a_idx,
                                    torch::Tensor b_idx, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IN(a_idx); CHECK_IN(b_idx); CHECK_IN(seg);
+  CHECK_IN(x); CHECK_IDX(a_idx); CHECK_IDX(b_idx); CHECK_IDX(seg);
+  TORCH_CHECK(x.dim() == 2, "segment_pair_maxdiff: x must be 2D");
+  TORCH_CHECK(a_idx.numel() == b_idx.numel(), "segment_pair_maxdiff: index lengths differ");
   long k = a_idx.numel(), d = x.size(1);
   int L = (int)seg.numel() - 1;
   auto out = torch::zeros({k, L}, torch::dtype(torch::kFloat32).device(x.device()));
@@ -420,6 +465,8 @@ static void launch_combine(torch::Tensor x, torch::Tensor rows, torch::Tensor w,
   long d = out.numel();
   TORCH_CHECK(d % 4 == 0 && stride_elems % 4 == 0 && col_off % 4 == 0,
               "combine: 16-byte alignment required");
+  TORCH_CHECK(w.numel() == rows.numel(), "combine: one weight per row index required");
+  TORCH_CHECK(x.dim() == 2 && d <= x.size(1), "combine: out is longer than a row of x");
   hipLaunchKernelGGL(k_combine, dim3(n_blocks(d / 4, NTHREADS)), dim3(NTHREADS), 0,
                      cur_stream(), (const float4 *)(x.data_ptr<float>() + col_off),
                      rows.data_ptr<long>(), w.data_ptr<float>(), (int)rows.numel(),
@@ -432,13 +479,13 @@ static void launch_combine(torch::Tensor x, torch::Tensor rows, torch::Tensor w,
 // combine, so bucketed and whole-row encodes are bit-identical.
 void combine_rows_slice(torch::Tensor x, torch::Tensor rows, torch::Tensor w,
                         torch::Tensor out, long col_off) {
-  CHECK_IN(x); CHECK_IN(rows); CHECK_IN(w); CHECK_IN(out);
+  CHECK_IN(x); CHECK_IDX(rows); CHECK_IN(w); CHECK_IN(out);
   TORCH_CHECK(col_off + out.numel() <= x.size(1), "combine slice out of range");
   launch_combine(x, rows, w, out, x.size(1), col_off);
 }
 
 void mean_rows(torch::Tensor x, torch::Tensor idx, torch::Tensor out) {
-  CHECK_IN(x); CHECK_IN(idx); CHECK_IN(out);
+  CHECK_IN(x); CHECK_IDX(idx); CHECK_IN(out);
   auto w = torch::full({idx.numel()}, 1.0 / (double)idx.numel(),
                        torch::dtype(torch::kFloat32).device(x.device()));
   launch_combine(x, idx, w, out, x.size(1));
@@ -475,10 +522,16 @@ __global__ void k_encode2(const float4 *__restrict__ g, const float *__restrict_
 
 void cyclic_encode(torch::Tensor grads, torch::Tensor w_re, torch::Tensor w_im,
                    torch::Tensor out) {
-  CHECK_IN(grads); CHECK_IN(out);
-  TORCH_CHECK(out.size(0) == 2, "cyclic_encode: out must be (2, d)");
+  CHECK_IN(grads); CHECK_IN(w_re); CHECK_IN(w_im); CHECK_IN(out);
+  TORCH_CHECK(grads.dim() == 2 && out.dim() == 2 && out.size(0) == 2,
+              "cyclic_encode: grads must be (k, d') and out (2, d)");
   long d = out.size(1);
   long stride = grads.size(1);
+  TORCH_CHECK(d % 4 == 0 && stride % 4 == 0,
+              "cyclic_encode: row lengths must be multiples of 4");
+  TORCH_CHECK(stride >= d, "cyclic_encode: grads rows are shorter than out rows");
+  TORCH_CHECK(w_re.numel() == grads.size(0) && w_im.numel() == grads.size(0),
+              "cyclic_encode: w_re and w_im need one weight per grads row");
   hipLaunchKernelGGL(k_encode2, dim3(n_blocks(d / 4, NTHREADS)), dim3(NTHREADS), 0,
                      cur_stream(), (const float4 *)grads.data_ptr<float>(),
                      w_re.data_ptr<float>(), w_im.data_ptr<float>(), (int)grads.size(0),
@@ -489,6 +542,10 @@ void cyclic_encode(torch::Tensor grads, torch::Tensor w_re, torch::Tensor w_im,
 void cyclic_recombine(torch::Tensor r_planes, torch::Tensor v_re, torch::Tensor v_im,
                       torch::Tensor out) {
   CHECK_IN(r_planes); CHECK_IN(out);
+  TORCH_CHECK(r_planes.dim() == 3 && r_planes.size(1) == 2,
+              "cyclic_recombine: r_planes must be (n, 2, d)");
+  TORCH_CHECK(v_re.numel() == r_planes.size(0) && v_im.numel() == r_planes.size(0),
+              "cyclic_recombine: v_re and v_im need one weight per worker");
   // rows (2i, 2i+1) are worker i's (re, im) planes; Re(v @ R) = sum vre*re - vim*im
   long n = r_planes.size(0);
   auto dev = r_planes.device();
@@ -533,6 +590,8 @@ torch::Tensor cyclic_project(torch::Tensor rows, torch::Tensor z) {
   TORCH_CHECK(rows.dim() == 2, "cyclic_project: rows must be 2D");
   long m = rows.size(0);
   long d = rows.size(1);
+  TORCH_CHECK(d % 4 == 0, "cyclic_project: row length must be a multiple of 4");
+  TORCH_CHECK(z.numel() == d, "cyclic_project: z must have the rows' length");
   auto out = torch::zeros({m}, torch::dtype(torch::kFloat32).device(rows.device()));
   if (d == 0) return out;
   dim3 grid(n_blocks(d / 4 / 8, NTHREADS), (unsigned)m);
@@ -544,7 +603,7 @@ torch::Tensor cyclic_project(torch::Tensor rows, torch::Tensor z) {
 }
 
 void combine_rows(torch::Tensor x, torch::Tensor rows, torch::Tensor w, torch::Tensor out) {
-  CHECK_IN(x); CHECK_IN(rows); CHECK_IN(w); CHECK_IN(out);
+  CHECK_IN(x); CHECK_IDX(rows); CHECK_IN(w); CHECK_IN(out);
   launch_combine(x, rows, w, out, x.size(1));
 }
 
@@ -598,7 +657,9 @@ __global__ void k_seg_sqdist(const float *__restrict__ x, const float *__restric
 }
 
 torch::Tensor segment_sqdist(torch::Tensor x, torch::Tensor z, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IN(z); CHECK_IN(seg);
+  CHECK_IN(x); CHECK_IN(z); CHECK_IDX(seg);
+  TORCH_CHECK(x.dim() == 2 && z.numel() == x.size(1),
+              "segment_sqdist: z must have the length of a row of x");
   long P = x.size(0), d = x.size(1);
   int L = (int)seg.numel() - 1;
   auto out = torch::zeros({P, L}, torch::dtype(torch::kFloat32).device(x.device()));
@@ -637,9 +698,12 @@ __global__ void k_seg_wmean(const float *__restrict__ x, const float *__restrict
 
 void segment_weighted_mean(torch::Tensor x, torch::Tensor w, torch::Tensor seg,
                            torch::Tensor out) {
-  CHECK_IN(x); CHECK_IN(w); CHECK_IN(seg); CHECK_IN(out);
+  CHECK_IN(x); CHECK_IN(w); CHECK_IDX(seg); CHECK_IN(out);
+  TORCH_CHECK(x.dim() == 2, "segment_weighted_mean: x must be 2D");
   long P = x.size(0), d = x.size(1);
   int L = (int)seg.numel() - 1;
+  TORCH_CHECK(w.numel() == P * L, "segment_weighted_mean: w must be (P, L)");
+  TORCH_CHECK(out.numel() >= d, "segment_weighted_mean: out is shorter than a row of x");
   if (d == 0) return;
   hipLaunchKernelGGL(k_seg_wmean, dim3(n_blocks(d, NTHREADS)), dim3(NTHREADS),
                      (L + 1) * sizeof(long), cur_stream(), x.data_ptr<float>(),
@@ -693,7 +757,7 @@ __global__ void k_seg_gram(const float *__restrict__ x, const long *__restrict__
 }
 
 torch::Tensor segment_gram(torch::Tensor x, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IN(seg);
+  CHECK_IN(x); CHECK_IDX(seg);
   long P = x.size(0), d = x.size(1);
   int L = (int)seg.numel() - 1;
   TORCH_CHECK(P <= 32, "segment_gram kernel supports P <= 32");

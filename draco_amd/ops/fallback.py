@@ -129,20 +129,32 @@ def rows_equal(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, atol: 
     return (diff <= atol).to(torch.uint8)
 
 
+def _absmax_nonfinite_inf(v: torch.Tensor, dim: int) -> torch.Tensor:
+    """max|v| along dim under the vote statistics' non-finite rule: any NaN, +Inf or
+    -Inf element (Inf - Inf = NaN included) makes the result exactly +inf, so a
+    non-finite member is never "equal" to anyone and the value survives a cross-rank
+    MAX allreduce (NaN ordering there is unspecified; +inf's is not)."""
+    a = v.abs()
+    a = torch.where(torch.isnan(a), torch.full_like(a, float("inf")), a)
+    return a.amax(dim=dim).float()
+
+
 @torch.no_grad()
 def pair_maxdiff(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor) -> torch.Tensor:
-    """Per-pair max|x[a]-x[b]| over the local shard.  (k,) fp32."""
+    """Per-pair max|x[a]-x[b]| over the local shard.  (k,) fp32; +inf if any element
+    of the difference is non-finite."""
     if x.shape[1] == 0:
         return torch.zeros(len(a_idx), dtype=torch.float32, device=x.device)
-    return (x[a_idx] - x[b_idx]).abs().amax(dim=1).float()
+    return _absmax_nonfinite_inf(x[a_idx] - x[b_idx], 1)
 
 
 @torch.no_grad()
 def row_absmax(x: torch.Tensor) -> torch.Tensor:
-    """Per-row max|x| over the local shard.  (m,) fp32."""
+    """Per-row max|x| over the local shard.  (m,) fp32; +inf if any element is
+    non-finite."""
     if x.shape[1] == 0:
         return torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
-    return x.abs().amax(dim=1).float()
+    return _absmax_nonfinite_inf(x, 1)
 
 
 @torch.no_grad()
@@ -216,13 +228,14 @@ def cyclic_recombine(r_planes: torch.Tensor, v_re: torch.Tensor, v_im: torch.Ten
 # --------------------------------------------------------------------- geo-median
 @torch.no_grad()
 def segment_absmax(x: torch.Tensor, seg: torch.Tensor) -> torch.Tensor:
-    """(rows, d), (L+1,) bounds -> (rows, L) per-segment max|x| (segment vote)."""
+    """(rows, d), (L+1,) bounds -> (rows, L) per-segment max|x| (segment vote); a
+    cell is +inf if its segment holds any non-finite element."""
     L = seg.numel() - 1
     out = torch.zeros(x.shape[0], L, dtype=torch.float32, device=x.device)
     for l in range(L):
         lo, hi = int(seg[l]), int(seg[l + 1])
         if hi > lo:
-            out[:, l] = x[:, lo:hi].abs().amax(dim=1)
+            out[:, l] = _absmax_nonfinite_inf(x[:, lo:hi], 1)
     return out
 
 

@@ -216,6 +216,12 @@ class VoteAggregator(Aggregator):
     curve; anything outside the ball loses the vote.  granularity="segment"
     tightens the ball to per parameter tensor (atol + rtol*max|g_seg| on EVERY
     segment; honest noise margin measured in profiles/segnoise_r02.txt).
+
+    Non-finite members: a member with ANY NaN, +Inf or -Inf value is outside every
+    ball.  The vote statistics report +inf for a pair (or segment) that touches a
+    non-finite element, and a pair is equal only if its statistic is finite — without
+    that, rtol > 0 gives thresh = atol + rtol*inf = inf and "inf <= inf" would admit
+    the member.  The test stays on device (no host read).
     """
 
     name = "maj_vote"
@@ -303,7 +309,7 @@ class VoteAggregator(Aggregator):
             segmax = stats[segdiff.numel():].view(recv.shape[0], -1)
             thresh = self.atol + self.rtol * torch.maximum(segmax[self.pairs_a],
                                                            segmax[self.pairs_b])
-            eq = (segdiff <= thresh).all(dim=1)
+            eq = (segdiff <= thresh).all(dim=1) & torch.isfinite(segdiff).all(dim=1)
         elif self.rtol > 0.0:
             maxdiff = ops.pair_maxdiff(recv, self.pairs_a, self.pairs_b)  # (n_pairs,)
             rowmax = ops.row_absmax(recv)  # (world*r,)
@@ -311,11 +317,11 @@ class VoteAggregator(Aggregator):
             self.comm.all_reduce(stats, op="max")  # full-gradient maxima
             maxdiff, rowmax = stats[: len(maxdiff)], stats[len(maxdiff):]
             thresh = self.atol + self.rtol * torch.maximum(rowmax[self.pairs_a], rowmax[self.pairs_b])
-            eq = maxdiff <= thresh
+            eq = (maxdiff <= thresh) & torch.isfinite(maxdiff)
         else:
             maxdiff = ops.pair_maxdiff(recv, self.pairs_a, self.pairs_b)
             self.comm.all_reduce(maxdiff, op="max")
-            eq = maxdiff <= self.atol
+            eq = (maxdiff <= self.atol) & torch.isfinite(maxdiff)
         # winner selection ON DEVICE (every rank computes the identical winners from
         # the identical allreduced bits — zero host round-trips in the decode):
         # the winner of group g is a member of its largest equality class.  When a

@@ -1,5 +1,6 @@
 """CPU op semantics vs independent oracles (torch.optim / numpy)."""
 import numpy as np
+import pytest
 import torch
 
 from draco_amd.ops import fallback as fb
@@ -140,3 +141,98 @@ def test_segment_ops_match_bruteforce():
         lo, hi = int(seg[l]), int(seg[l + 1])
         ref = x[:, lo:hi] @ x[:, lo:hi].T
         assert torch.allclose(gram[l], ref, atol=1e-4)
+
+
+# ----------------------------------------------------------- non-finite vote statistics
+# Rule (ops/fallback.py:_absmax_nonfinite_inf): any NaN / +Inf / -Inf element in the
+# reduced range makes that cell exactly +inf; every other cell keeps its clean bits.
+_NF_D = 48
+_NF_SEG = torch.tensor([4, 10, 10, 30, 44])  # lead gap, empty, middle [10, 30), trail gap
+_NF_A = torch.tensor([0, 1, 3, 0])
+_NF_B = torch.tensor([2, 3, 4, 2])  # pair 3 repeats pair 0
+
+
+def _nf_clean():
+    g = torch.Generator().manual_seed(5)
+    return torch.rand(5, _NF_D, generator=g) * 2 - 1
+
+
+def _nf_stats(x):
+    return {
+        "row_absmax": fb.row_absmax(x),
+        "pair_maxdiff": fb.pair_maxdiff(x, _NF_A, _NF_B),
+        "segment_absmax": fb.segment_absmax(x, _NF_SEG),
+        "segment_pair_maxdiff": fb.segment_pair_maxdiff(x, _NF_A, _NF_B, _NF_SEG),
+    }
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _nf_expect(clean, row, cols):
+    """Expected statistics: clean ones with +inf written to every cell whose reduced
+    range holds a planted element of `row`."""
+    exp = {k: v.clone() for k, v in clean.items()}
+    inf = float("inf")
+    exp["row_absmax"][row] = inf
+    pairs = [k for k in range(len(_NF_A)) if row in (int(_NF_A[k]), int(_NF_B[k]))]
+    for k in pairs:
+        exp["pair_maxdiff"][k] = inf
+    for c in cols:
+        for l in range(len(_NF_SEG) - 1):
+            if int(_NF_SEG[l]) <= c < int(_NF_SEG[l + 1]):
+                exp["segment_absmax"][row, l] = inf
+                for k in pairs:
+                    exp["segment_pair_maxdiff"][k, l] = inf
+    return exp
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+@pytest.mark.parametrize("col", [0, _NF_D - 1, 17, 4, 29, 30])
+def test_vote_statistics_nonfinite_rule(bad, col):
+    """col 0 / d-1: first and last element of the row (both in a segment gap);
+    17: inside the middle segment; 4, 29: first/last element of a segment; 30: the
+    first element after the middle segment."""
+    x = _nf_clean()
+    clean = _nf_stats(x)
+    x[2, col] = bad
+    got = _nf_stats(x)
+    exp = _nf_expect(clean, 2, [col])
+    for name in exp:
+        assert torch.equal(_bits(got[name]), _bits(exp[name])), (name, got[name], exp[name])
+
+
+def test_vote_statistics_inf_minus_inf_counts_as_nonfinite():
+    """+Inf at the same column of BOTH rows of a pair: the difference is NaN there
+    and must still read +inf; a pair whose rows are both clean stays bit-equal."""
+    x = _nf_clean()
+    clean = _nf_stats(x)
+    x[0, 17] = float("inf")
+    x[2, 17] = float("inf")
+    got = _nf_stats(x)
+    exp = _nf_expect(_nf_expect(clean, 0, [17]), 2, [17])
+    for name in exp:
+        assert torch.equal(_bits(got[name]), _bits(exp[name])), (name, got[name], exp[name])
+    assert got["pair_maxdiff"][0] == float("inf") and got["pair_maxdiff"][3] == float("inf")
+    assert torch.isfinite(got["pair_maxdiff"][1:3]).all()
+
+
+def test_vote_statistics_whole_row_nonfinite():
+    x = _nf_clean()
+    clean = _nf_stats(x)
+    x[3] = float("nan")
+    got = _nf_stats(x)
+    exp = _nf_expect(clean, 3, list(range(_NF_D)))
+    for name in exp:
+        assert torch.equal(_bits(got[name]), _bits(exp[name])), (name, got[name], exp[name])
+
+
+def test_rows_equal_treats_nan_as_unequal():
+    x = _nf_clean()
+    x[2] = x[0]
+    a, b = torch.tensor([0, 0]), torch.tensor([2, 1])
+    assert fb.rows_equal(x, a, b, 0.0).tolist() == [1, 0]
+    x[2, 17] = float("nan")
+    assert fb.rows_equal(x, a, b, 0.0).tolist() == [0, 0]
+    assert fb.rows_equal(x, a, b, 1e9).tolist() == [0, 1]

@@ -149,3 +149,72 @@ def test_segment_vote_neutralizes_within_tol_attack_e2e():
     la, lc = attacked[0][0], clean[0][0]
     assert attacked[0][1] == attacked[1][1] == attacked[2][1]
     assert abs(la[-1] - lc[-1]) < 0.1, f"attacked {la[-1]:.3f} vs clean {lc[-1]:.3f}"
+
+
+# ------------------------------------------------------------- non-finite adversaries
+NONFINITE = {"nan": float("nan"), "+inf": float("inf"), "-inf": float("-inf")}
+
+
+def nonfinite_vote_case(device, granularity, rtol, bad_slots, bad, plant):
+    """One 3-member group (atol=1e-3) whose members all hold the same honest g, then
+    the members in `bad_slots` get `bad` planted at element 7 or over the whole row.
+    Shared with the on-device run in tests/test_kernels_gpu_edges.py."""
+    device = torch.device(device)
+    comm = Communicator(0, 1, device)
+    space = FlatSpace(TwoScale(), 1, device)
+    agg = VoteAggregator(comm, space, group_size=3, atol=1e-3, rtol=rtol,
+                         member_rows=np.array([[0, 1, 2]]), granularity=granularity)
+    gen = torch.Generator().manual_seed(0)
+    g = torch.zeros(space.d_pad)
+    g[:1000] = torch.randn(1000, generator=gen) * 50.0
+    g[1000:1020] = torch.randn(20, generator=gen) * 0.01
+    g = g.to(device)
+    payload = space.alloc_payload(3)
+    payload[:] = g
+    for slot in bad_slots:
+        if plant == "element":
+            payload[slot, 7] = bad
+        else:
+            payload[slot, :] = bad
+    out = agg.aggregate(payload, step=0)
+    return out, g, agg
+
+
+NONFINITE_GRID = [
+    pytest.param(gran, rtol, bad, plant, slot, id=f"{gran}-rtol{rtol}-{bad}-{plant}-slot{slot}")
+    for gran in ("row", "segment") for rtol in (0.0, 0.1) for bad in NONFINITE
+    for plant in ("element", "row") for slot in (0, 2)
+]
+
+
+@pytest.mark.parametrize("granularity,rtol,bad,plant,slot", NONFINITE_GRID)
+def test_nonfinite_adversary_loses_the_vote(granularity, rtol, bad, plant, slot):
+    """A member holding any NaN/+Inf/-Inf is outside every ball: the two honest
+    members form the majority class even when the adversary sits in slot 0 (the
+    tie-break winner), with rtol > 0 (thresh = atol + rtol*inf = inf must not admit
+    it) and under both granularities."""
+    out, g, agg = nonfinite_vote_case("cpu", granularity, rtol, [slot], NONFINITE[bad], plant)
+    assert torch.isfinite(out).all()
+    assert torch.equal(out, g), float((out - g).abs().max())
+    assert agg.degenerate_steps == 0
+
+
+@pytest.mark.parametrize("granularity,rtol", [("row", 0.0), ("row", 0.1), ("segment", 0.1)])
+@pytest.mark.parametrize("honest", [0, 1, 2])
+def test_two_nonfinite_members_are_flagged_degenerate(granularity, rtol, honest):
+    """Two of three members non-finite (beyond the code's tolerance s=1): no pair has
+    a finite statistic, so every equality class has size 1 and the group has no
+    equal pair.  Observed behaviour, pinned here: the step is counted in
+    degenerate_steps (exactly 1 — never a silent loss), and the pick falls to the
+    deterministic tie-break, member slot 0.  So the honest gradient comes out
+    bit-exactly iff the honest member sits in slot 0; otherwise the aggregate is
+    non-finite, which the trainer's nan-guard then skips."""
+    bad_slots = [s for s in range(3) if s != honest]
+    out, g, agg = nonfinite_vote_case("cpu", granularity, rtol, bad_slots,
+                                      float("nan"), "element")
+    assert agg.degenerate_steps == 1
+    if honest == 0:
+        assert torch.equal(out, g)
+    else:
+        assert not torch.isfinite(out).all()
+        assert not torch.isfinite(out[7])
