@@ -19,7 +19,8 @@ class Config:
     momentum: float = 0.5
     seed: int = 1
     network: str = "LeNet"            # LeNet|FC|ResNet18|ResNet34|ResNet50|ResNet101|ResNet152|VGG11|VGG13|VGG16|VGG19
-    mode: str = "normal"              # normal|geometric_median|krum|maj_vote|cyclic (aggregation rule)
+    mode: str = "normal"              # normal|geometric_median|krum|median|trimmed_mean|maj_vote|cyclic
+                                      # (aggregation rule; trimmed_mean drops worker_fail per end)
     dataset: str = "MNIST"            # MNIST|Cifar10|ImageNetSynthetic
     comm_type: str = "Bcast"          # accepted for parity; collectives are always fused (README.md:111)
     err_mode: str = "rev_grad"        # rev_grad|constant|random|gauss|none
@@ -37,7 +38,8 @@ class Config:
 
     # MI355X-native extensions
     topology: str = "colocated"       # colocated (all ranks compute) | ps (rank0 = parameter server)
-    workers_per_rank: int = 0         # 0 = derive from approach (r for maj_vote, 1 otherwise)
+    workers_per_rank: int = 0         # 0 = derive from approach (r for maj_vote, 1 for baseline);
+                                      # baseline and cyclic host this many logical workers per rank
     vote_atol: float = 0.0            # absolute vote tolerance (0.0 = reference bitwise semantics)
     vote_rtol: float = -1.0           # relative vote tolerance; -1 = auto (0 on CPU, 1e-3 on GPU --
                                       # MIOpen conv backward is not bitwise-reproducible; see

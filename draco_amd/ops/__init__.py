@@ -28,6 +28,7 @@ __all__ = [
     "segment_sqdist",
     "segment_weighted_mean",
     "segment_gram",
+    "column_trimmed_mean",
     "available",
 ]
 
@@ -198,3 +199,13 @@ def segment_gram(x, seg):
     if ext is not None:
         return ext.segment_gram(x, seg.to(x.device))
     return fallback.segment_gram(x, seg)
+
+
+def column_trimmed_mean(x, lo, hi, out):
+    """out[j] = mean of sorted ranks [lo, hi) of column j (NaN sorts as +inf):
+    coordinate-wise median (lo=(P-1)//2, hi=P//2+1) and trimmed mean (lo=b, hi=P-b)."""
+    ext = _native_for(x)
+    if ext is not None:
+        ext.column_trimmed_mean(x, int(lo), int(hi), out)
+        return
+    fallback.column_trimmed_mean(x, int(lo), int(hi), out)

@@ -292,6 +292,34 @@ def segment_gram(x: torch.Tensor, seg: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# --------------------------------------------------------------------- trimmed mean
+@torch.no_grad()
+def column_trimmed_mean(x: torch.Tensor, lo: int, hi: int, out: torch.Tensor) -> None:
+    """out[j] = mean of ranks [lo, hi) of column j of x (coordinate-wise median /
+    beta-trimmed mean, arXiv:1803.01498).
+
+    x: (P, d) fp32; out: (d,); 0 <= lo < hi <= P.  Per column: NaN -> +inf (the vote
+    statistics' rule: a NaN is an extreme value that gets trimmed), ascending sort,
+    then the kept ranks are added ONE AT A TIME in ascending order and divided by
+    float32(hi - lo).  The HIP kernel performs the same fp32 operations in the same
+    order, so the two agree bit for bit (torch.sum/mean have an unspecified order).
+    """
+    P = x.shape[0]
+    if not 0 <= lo < hi <= P:
+        raise ValueError(f"column_trimmed_mean needs 0 <= lo < hi <= P, got lo={lo} hi={hi} P={P}")
+    if out.numel() != x.shape[1]:
+        raise ValueError("column_trimmed_mean: out must have the length of a row of x")
+    if x.shape[1] == 0:
+        return
+    a = torch.where(torch.isnan(x), torch.full_like(x, float("inf")), x)
+    s, _ = torch.sort(a, dim=0)
+    acc = s[lo].clone()
+    for k in range(lo + 1, hi):
+        acc = acc + s[k]
+    # tensor divisor: an elementwise IEEE division (never a multiply by 1/k)
+    torch.div(acc, torch.full_like(acc, float(hi - lo)), out=out)
+
+
 # --------------------------------------------------------------------- dtype cast
 @torch.no_grad()
 def cast_to_bf16(x: torch.Tensor, out: torch.Tensor) -> None:

@@ -3,6 +3,7 @@ from .aggregators import (
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
+    TrimmedMeanAggregator,
     VoteAggregator,
 )
 from .comm import Communicator
@@ -17,5 +18,6 @@ __all__ = [
     "VoteAggregator",
     "GeoMedianAggregator",
     "KrumAggregator",
+    "TrimmedMeanAggregator",
     "CyclicAggregator",
 ]

@@ -10,6 +10,8 @@ all_gather of the decoded shard.  Reference semantics per policy:
   maj_vote     rep_master.py:141-168                (group-wise Boyer-Moore vote)
   geo_median   baseline_master.py:271-276           (per-layer Weiszfeld)
   krum         baseline_master.py:278-296           (per-layer Krum selection)
+  median       (not in the reference) arXiv:1803.01498  (coordinate-wise median)
+  trimmed_mean (not in the reference) arXiv:1803.01498  (coordinate-wise b-trimmed mean)
   cyclic       cyclic_master.py:103-188             (DFT-code algebraic decode)
 """
 from __future__ import annotations
@@ -452,6 +454,57 @@ class KrumAggregator(Aggregator):
         if self._tail < out.shape[0]:
             out[self._tail:] = 0.0
         self.comm.all_gather_shard(out, self._out)
+        return self._out
+
+
+class TrimmedMeanAggregator(Aggregator):
+    """Coordinate-wise median / beta-trimmed mean (arXiv:1803.01498), sharded over d.
+
+    Purely per-coordinate, so the rule commutes with sharding exactly: all_to_all,
+    ONE kernel on the local shard (per-column sort of the P received values, mean of
+    the kept ranks), all_gather — no cross-shard allreduce, no host read.
+
+    trim=None is the median (mean of the two middle values for even P); trim=b drops
+    the b smallest and b largest values of every coordinate.  With at most b
+    corrupted workers every output coordinate lies inside the honest workers'
+    [min, max], whatever the adversary sends: a NaN sorts as +inf and is trimmed like
+    any other extreme.  (More non-finite rows than trim can still yield inf/NaN —
+    the trainer's nan-guard then skips the update.)
+    """
+
+    MAX_WORKERS = 64  # the kernel sorts a column in registers, padded to <= 64 rows
+
+    def __init__(self, comm, space, num_workers: int, trim: int | None = None):
+        super().__init__(comm, space)
+        self.num_workers = num_workers
+        self.trim = trim
+        self.name = "median" if trim is None else "trimmed_mean"
+        if num_workers > self.MAX_WORKERS:
+            # CPU-side config check (as for Krum): fail at construction, not at the
+            # first kernel launch on the GPU
+            raise ValueError(
+                f"TrimmedMeanAggregator supports at most {self.MAX_WORKERS} workers "
+                f"(got {num_workers}): the column-sort HIP kernel holds a column in registers")
+        if trim is not None and trim < 0:
+            raise ValueError(f"trim must be >= 0, got {trim}")
+        self._bounds(num_workers)
+
+    def _bounds(self, P: int):
+        """Kept rank range [lo, hi) for P received rows (computed per call: the
+        survivor world after a rank failure has fewer rows)."""
+        if self.trim is None:
+            return (P - 1) // 2, P // 2 + 1
+        if 2 * self.trim >= P:
+            raise ValueError(
+                f"trimmed mean with trim={self.trim} per end needs more than "
+                f"{2 * self.trim} workers, got {P}")
+        return self.trim, P - self.trim
+
+    def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
+        recv = self.exchanged(payload)  # (P, shard)
+        lo, hi = self._bounds(recv.shape[0])
+        ops.column_trimmed_mean(recv, lo, hi, self._shard_out)
+        self.comm.all_gather_shard(self._shard_out, self._out)
         return self._out
 
 

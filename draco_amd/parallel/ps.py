@@ -33,6 +33,7 @@ from .aggregators import (
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
+    TrimmedMeanAggregator,
     VoteAggregator,
 )
 from .comm import Communicator
@@ -130,8 +131,14 @@ class Master(_PSBase):
                 self.agg = GeoMedianAggregator(local, self.space, num_workers=self.P)
             elif cfg.mode == "krum":
                 self.agg = KrumAggregator(local, self.space, num_workers=self.P, s=cfg.worker_fail)
+            elif cfg.mode == "median":
+                self.agg = TrimmedMeanAggregator(local, self.space, num_workers=self.P)
+            elif cfg.mode == "trimmed_mean":
+                self.agg = TrimmedMeanAggregator(local, self.space, num_workers=self.P,
+                                                 trim=cfg.worker_fail)
             else:
-                raise ValueError(cfg.mode)
+                raise ValueError("baseline approach supports modes normal/geometric_median/krum/"
+                                 f"median/trimmed_mean, got {cfg.mode!r}")
         elif cfg.approach == "maj_vote":
             r = cfg.group_size
             if self.P % r != 0:

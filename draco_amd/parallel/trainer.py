@@ -36,6 +36,7 @@ from .aggregators import (
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
+    TrimmedMeanAggregator,
     VoteAggregator,
 )
 from .comm import Communicator
@@ -118,8 +119,11 @@ class Trainer:
         approach = cfg.approach
         self.approach = approach
         if approach == "baseline":
-            self.L = 1
-            self.P = self.world
+            # one logical worker per rank unless workers_per_rank asks for more (a
+            # single process then hosts P = L workers, so the order-statistic rules
+            # and their adversaries can be exercised without P ranks)
+            self.L = max(cfg.workers_per_rank, 1)
+            self.P = self.L * self.world
             self.data = GroupBatchSource(self._dataset(), cfg.batch_size, n_groups=self.P)
         elif approach == "maj_vote":
             self.r = cfg.group_size
@@ -249,7 +253,14 @@ class Trainer:
             return GeoMedianAggregator(self.comm, self.space, num_workers=num_workers)
         if cfg.mode == "krum":
             return KrumAggregator(self.comm, self.space, num_workers=num_workers, s=cfg.worker_fail)
-        raise ValueError(f"baseline approach supports modes normal/geometric_median/krum, got {cfg.mode!r}")
+        if cfg.mode == "median":
+            return TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers)
+        if cfg.mode == "trimmed_mean":
+            # trim = the tolerated adversary count, as Krum takes s = worker_fail
+            return TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers,
+                                         trim=cfg.worker_fail)
+        raise ValueError("baseline approach supports modes normal/geometric_median/krum/"
+                         f"median/trimmed_mean, got {cfg.mode!r}")
 
     def _setup_decode(self) -> None:
         """Build the aggregator + comm-layout buffers for the CURRENT communicator
@@ -258,7 +269,7 @@ class Trainer:
         cfg = self.cfg
         alive = self.health.alive if self.health is not None else list(range(self.world))
         if self.approach == "baseline":
-            self.agg = self._baseline_aggregator(cfg, num_workers=len(alive))
+            self.agg = self._baseline_aggregator(cfg, num_workers=self.L * len(alive))
             self.payload = self.space.alloc_payload(self.L)
         elif self.approach == "maj_vote":
             from ..coding import colocated_member_rows
@@ -583,8 +594,8 @@ class Trainer:
             pending = []
             for l in range(self.L):
                 if self.approach == "baseline":
-                    group = self.rank  # every worker draws its own stream
-                    worker_id = self.rank
+                    worker_id = l * self.world + self.rank  # l-major global worker id
+                    group = worker_id  # every worker draws its own stream
                 else:
                     group = (self.rank - l) % self.world
                     worker_id = l * self.world + self.rank  # l-major global worker id

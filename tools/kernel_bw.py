@@ -90,6 +90,33 @@ def main():
     report("segment_weighted_mean", ms, B + 4 * d)
     ms = t_ms(lambda: ops.segment_gram(x, seg))
     report("segment_gram (krum)", ms, B)
+    ms = t_ms(lambda: ops.column_trimmed_mean(x, 11, 13, out))
+    report("column_trimmed_mean (median)", ms, B + 4 * d)
+    ms = t_ms(lambda: ops.column_trimmed_mean(x, 1, 23, out))
+    report("column_trimmed_mean (b=1)", ms, B + 4 * d)
+
+
+def trimmed_mean_compare():
+    """column_trimmed_mean vs its two yardsticks on the same shape: the torch route to
+    the same result (sort along dim 0, slice, mean) and combine_rows, which reads the
+    same bytes and writes the same output (the streaming ceiling for this access
+    pattern)."""
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    rows = 24
+    x = torch.randn(rows, d, device=DEV)
+    out = torch.empty(d, device=DEV)
+    B = 4 * rows * d + 4 * d
+    idx = torch.arange(rows, device=DEV)
+    w = torch.randn(rows, device=DEV)
+    ms = t_ms(lambda: ops.combine_rows(x, idx, w, out))
+    report("combine_rows (24 rows)", ms, B)
+    for name, lo, hi in (("median", 11, 13), ("b=1", 1, 23)):
+        ms = t_ms(lambda: ops.column_trimmed_mean(x, lo, hi, out))
+        report(f"column_trimmed_mean ({name})", ms, B)
+        ms = t_ms(lambda: torch.mean(torch.sort(x, dim=0).values[lo:hi], dim=0, out=out),
+                  iters=5, warmup=2)
+        report(f"torch sort+mean ({name})", ms, B)
 
 
 def gram_compare():
@@ -111,5 +138,8 @@ def gram_compare():
 if __name__ == "__main__":
     if os.environ.get("GRAM_ONLY") == "1":
         gram_compare()
+        raise SystemExit(0)
+    if os.environ.get("TRIMMED_MEAN_ONLY") == "1":
+        trimmed_mean_compare()
         raise SystemExit(0)
     main()
