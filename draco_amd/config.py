@@ -19,8 +19,10 @@ class Config:
     momentum: float = 0.5
     seed: int = 1
     network: str = "LeNet"            # LeNet|FC|ResNet18|ResNet34|ResNet50|ResNet101|ResNet152|VGG11|VGG13|VGG16|VGG19
-    mode: str = "normal"              # normal|geometric_median|krum|median|trimmed_mean|maj_vote|cyclic
-                                      # (aggregation rule; trimmed_mean drops worker_fail per end)
+    mode: str = "normal"              # normal|geometric_median|krum|median|trimmed_mean|meamed|phocas|
+                                      # maj_vote|cyclic (aggregation rule; trimmed_mean drops
+                                      # worker_fail per end; meamed/phocas keep the P-worker_fail
+                                      # values nearest the median / the worker_fail-trimmed mean)
     dataset: str = "MNIST"            # MNIST|Cifar10|ImageNetSynthetic
     comm_type: str = "Bcast"          # accepted for parity; collectives are always fused (README.md:111)
     err_mode: str = "rev_grad"        # rev_grad|constant|random|gauss|none

@@ -29,6 +29,7 @@ __all__ = [
     "segment_weighted_mean",
     "segment_gram",
     "column_trimmed_mean",
+    "column_mean_around",
     "available",
 ]
 
@@ -209,3 +210,15 @@ def column_trimmed_mean(x, lo, hi, out):
         ext.column_trimmed_mean(x, int(lo), int(hi), out)
         return
     fallback.column_trimmed_mean(x, int(lo), int(hi), out)
+
+
+def column_mean_around(x, keep, clo, chi, out):
+    """out[j] = mean of the `keep` values of column j nearest to the centre c = mean of
+    sorted ranks [clo, chi) (NaN sorts as +inf): mean around median (clo=(P-1)//2,
+    chi=P//2+1) and Phocas (clo=b, chi=P-b), keep = P-b.  Definition, the radius
+    guarantee and the missing envelope guarantee: fallback.column_mean_around."""
+    ext = _native_for(x)
+    if ext is not None:
+        ext.column_mean_around(x, int(keep), int(clo), int(chi), out)
+        return
+    fallback.column_mean_around(x, int(keep), int(clo), int(chi), out)

@@ -6,7 +6,10 @@
 // flat gradient space (d up to ~10^7 fp32 per model replica), so the design rules are
 // the memory ones from the CDNA4 guide: 256-thread blocks (4 waves of 64), float4
 // (16 B/lane) vectorized access, grid-stride loops capped at ~2048 blocks, wave-level
-// __shfl reductions (wave = 64 lanes on CDNA4, not 32).
+// __shfl reductions (wave = 64 lanes on CDNA4, not 32).  The exceptions are the two
+// column-sort kernels at the end (k_col_trimmed_mean: median / trimmed mean;
+// k_col_mean_around: mean around median / Phocas), which sort each column in registers
+// and are VALU-heavy.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -896,6 +899,106 @@ void column_trimmed_mean(torch::Tensor x, long lo, long hi, torch::Tensor out) {
 #undef LAUNCH_CTM
 }
 
+// --------------------------------------------------------------------------- mean around
+// Mean around median ("MeaMed", Xie et al., arXiv:1802.10116) and Phocas
+// (arXiv:1805.09682): per column, the mean of the `keep` values nearest to a robust
+// centre c — the median (clo=(P-1)/2, chi=P/2+1) or the b-trimmed mean (clo=b,
+// chi=P-b), b = P - keep.  Same layout, padding and register sort as
+// k_col_trimmed_mean; c is that kernel's arithmetic on ranks [clo, chi).
+//
+// The `keep` nearest values of a sorted column are a contiguous window s[w, w+keep).
+// Its start is a count, not a search:  w = #{ j < b : (c - s[j]) > (s[j+keep] - c) }
+// (the predicate is monotone in j; a tie keeps the lower value, a NaN compares false).
+// s[j + keep] has a run-time offset, and a run-time-indexed per-thread array goes to
+// scratch, so t[j] = s[j + keep] is built by a barrel shifter: stage q moves every
+// element down by 1<<q if bit q of keep is set — compile-time indices, wave-uniform
+// conditions, registers only.  The window is then summed ascending with a per-lane
+// select between acc and acc + s[r] (never "+ 0", which would turn a -0 result into
+// +0), so the result is bit-identical to the CPU fallback.
+template <int N>
+__global__ void __launch_bounds__(NTHREADS)
+k_col_mean_around(const float *__restrict__ x, int P, int keep, int clo, int chi,
+                  float ccnt, float kcnt, float *__restrict__ out, long d, long stride) {
+  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  long gstride = gridDim.x * (long)blockDim.x;
+  const int b = P - keep;
+  for (; i < d; i += gstride) {
+    float s[N];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      float v = INFINITY;
+      if (p < P) {
+        v = x[p * stride + i];
+        v = (v != v) ? INFINITY : v;
+      }
+      s[p] = v;
+    }
+    sort_columns(s, std::make_integer_sequence<int, kMergeExchange<N>.n>{});
+    float c = -0.f;
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+      if (r >= clo && r < chi) c += s[r];
+    c = c / ccnt;
+    // t[j] = s[j + keep] (+inf past the end: never compared, since j + keep < P for j < b)
+    float t[N];
+#pragma unroll
+    for (int r = 0; r < N; ++r) t[r] = s[r];
+#pragma unroll
+    for (int q = 0; (1 << q) <= N; ++q) {
+      if (keep & (1 << q)) {
+#pragma unroll
+        for (int r = 0; r < N; ++r) t[r] = (r + (1 << q) < N) ? t[r + (1 << q)] : INFINITY;
+      }
+    }
+    int w = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (j < b) w += ((c - s[j]) > (t[j] - c)) ? 1 : 0;
+    const int wend = w + keep;
+    float acc = -0.f;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+      float nxt = acc + s[r];
+      acc = (r >= w && r < wend) ? nxt : acc;
+    }
+    out[i] = acc / kcnt;
+  }
+}
+
+void column_mean_around(torch::Tensor x, long keep, long clo, long chi, torch::Tensor out) {
+  CHECK_IN(x); CHECK_IN(out);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 && out.scalar_type() == torch::kFloat32,
+              "column_mean_around: x and out must be fp32");
+  TORCH_CHECK(x.dim() == 2, "column_mean_around: x must be 2D");
+  long P = x.size(0), d = x.size(1);
+  TORCH_CHECK(P >= 1 && P <= 64, "column_mean_around kernel supports 1 <= P <= 64, got ", P);
+  TORCH_CHECK(1 <= keep && keep <= P,
+              "column_mean_around: need 1 <= keep <= P, got keep=", keep, " P=", P);
+  TORCH_CHECK(0 <= clo && clo < chi && chi <= P,
+              "column_mean_around: need 0 <= clo < chi <= P, got clo=", clo, " chi=", chi,
+              " P=", P);
+  TORCH_CHECK(out.numel() == d, "column_mean_around: out must have the length of a row of x");
+  TORCH_CHECK(d % 4 == 0, "column_mean_around: row length must be a multiple of 4");
+  if (d == 0) return;
+  dim3 grid(n_blocks(d, NTHREADS));
+  hipStream_t s = cur_stream();
+  const float *xp = x.data_ptr<float>();
+  float *op = out.data_ptr<float>();
+  float ccnt = (float)(chi - clo), kcnt = (float)keep;
+#define LAUNCH_CMA(N) \
+  hipLaunchKernelGGL((k_col_mean_around<N>), grid, dim3(NTHREADS), 0, s, xp, (int)P, \
+                     (int)keep, (int)clo, (int)chi, ccnt, kcnt, op, d, d)
+  if (P <= 4) LAUNCH_CMA(4);
+  else if (P <= 8) LAUNCH_CMA(8);
+  else if (P <= 12) LAUNCH_CMA(12);
+  else if (P <= 16) LAUNCH_CMA(16);
+  else if (P <= 24) LAUNCH_CMA(24);
+  else if (P <= 32) LAUNCH_CMA(32);
+  else if (P <= 48) LAUNCH_CMA(48);
+  else LAUNCH_CMA(64);
+#undef LAUNCH_CMA
+}
+
 // --------------------------------------------------------------------------- module
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd_step", &fused_sgd_step);
@@ -917,4 +1020,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segment_weighted_mean", &segment_weighted_mean);
   m.def("segment_gram", &segment_gram);
   m.def("column_trimmed_mean", &column_trimmed_mean);
+  m.def("column_mean_around", &column_mean_around);
 }

@@ -320,6 +320,70 @@ def column_trimmed_mean(x: torch.Tensor, lo: int, hi: int, out: torch.Tensor) ->
     torch.div(acc, torch.full_like(acc, float(hi - lo)), out=out)
 
 
+# --------------------------------------------------------------------- mean around
+@torch.no_grad()
+def mean_around_window(x: torch.Tensor, keep: int, clo: int, chi: int):
+    """Steps 1-3 of column_mean_around: (s, c, w) = the sorted columns, the centre and
+    the start of the kept window of every column (exposed so tests can see which
+    windows a data set exercises)."""
+    P = x.shape[0]
+    if not 1 <= keep <= P:
+        raise ValueError(f"column_mean_around needs 1 <= keep <= P, got keep={keep} P={P}")
+    if not 0 <= clo < chi <= P:
+        raise ValueError(
+            f"column_mean_around needs 0 <= clo < chi <= P, got clo={clo} chi={chi} P={P}")
+    a = torch.where(torch.isnan(x), torch.full_like(x, float("inf")), x)
+    s, _ = torch.sort(a, dim=0)
+    c = s[clo].clone()
+    for k in range(clo + 1, chi):
+        c = c + s[k]
+    # tensor divisor: an elementwise IEEE division (never a multiply by 1/k)
+    c = torch.div(c, torch.full_like(c, float(chi - clo)))
+    b = P - keep
+    if b > 0:
+        w = ((c - s[:b]) > (s[keep:] - c)).sum(dim=0)
+    else:
+        w = torch.zeros(x.shape[1], dtype=torch.long, device=x.device)
+    return s, c, w
+
+
+@torch.no_grad()
+def column_mean_around(x: torch.Tensor, keep: int, clo: int, chi: int,
+                       out: torch.Tensor) -> None:
+    """out[j] = mean of the `keep` values of column j nearest to a robust centre c
+    (mean around median, arXiv:1802.10116; Phocas, arXiv:1805.09682).
+
+    x: (P, d) fp32; out: (d,); 1 <= keep <= P; 0 <= clo < chi <= P; b = P - keep.
+    Per column:
+      1. NaN -> +inf, ascending sort into s[0..P)            (column_trimmed_mean's step)
+      2. c = column_trimmed_mean(x, clo, chi): ranks [clo, chi) added one at a time,
+         divided by float32(chi - clo).  Median: ((P-1)//2, P//2+1); trimmed mean: (b, P-b)
+      3. w = #{ j in [0, b) : (c - s[j]) > (s[j + keep] - c) } -- plain fp32, strict >,
+         a NaN comparison is false.  The predicate is monotone in j, and w is where
+         dropping, b times, whichever end is farther from c (a tie drops the top)
+         arrives: s[w, w+keep) holds the keep smallest distances to c
+      4. out = ranks [w, w+keep) added one at a time ascending / float32(keep)
+    The HIP kernel performs the same fp32 operations in the same order: bit-identical.
+
+    With at most b corrupted rows and P > 2b, c lies inside the honest [min, max] and
+    |out - c| <= max over honest h of |h - c| (the radius guarantee).  The output itself
+    is NOT confined to the honest [min, max]: a corrupted value just outside it can be
+    nearer to c than a far honest one.  With at most b non-finite rows the window holds
+    finite values only; with more the result may be inf/NaN.
+    """
+    s, _, w = mean_around_window(x, keep, clo, chi)
+    if out.numel() != x.shape[1]:
+        raise ValueError("column_mean_around: out must have the length of a row of x")
+    if x.shape[1] == 0:
+        return
+    idx = w.unsqueeze(0) + torch.arange(keep, device=x.device).unsqueeze(1)
+    win = torch.gather(s, 0, idx)
+    acc = win[0].clone()
+    for k in range(1, keep):
+        acc = acc + win[k]
+    torch.div(acc, torch.full_like(acc, float(keep)), out=out)
+
+
 # --------------------------------------------------------------------- dtype cast
 @torch.no_grad()
 def cast_to_bf16(x: torch.Tensor, out: torch.Tensor) -> None:

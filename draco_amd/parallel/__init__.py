@@ -3,6 +3,7 @@ from .aggregators import (
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
+    MeanAroundAggregator,
     TrimmedMeanAggregator,
     VoteAggregator,
 )
@@ -19,5 +20,6 @@ __all__ = [
     "GeoMedianAggregator",
     "KrumAggregator",
     "TrimmedMeanAggregator",
+    "MeanAroundAggregator",
     "CyclicAggregator",
 ]

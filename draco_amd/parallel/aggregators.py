@@ -12,6 +12,8 @@ all_gather of the decoded shard.  Reference semantics per policy:
   krum         baseline_master.py:278-296           (per-layer Krum selection)
   median       (not in the reference) arXiv:1803.01498  (coordinate-wise median)
   trimmed_mean (not in the reference) arXiv:1803.01498  (coordinate-wise b-trimmed mean)
+  meamed       (not in the reference) arXiv:1802.10116  (mean of the P-b values nearest the median)
+  phocas       (not in the reference) arXiv:1805.09682  (mean of the P-b values nearest the b-trimmed mean)
   cyclic       cyclic_master.py:103-188             (DFT-code algebraic decode)
 """
 from __future__ import annotations
@@ -504,6 +506,65 @@ class TrimmedMeanAggregator(Aggregator):
         recv = self.exchanged(payload)  # (P, shard)
         lo, hi = self._bounds(recv.shape[0])
         ops.column_trimmed_mean(recv, lo, hi, self._shard_out)
+        self.comm.all_gather_shard(self._shard_out, self._out)
+        return self._out
+
+
+class MeanAroundAggregator(Aggregator):
+    """Mean around median ("MeaMed", arXiv:1802.10116) and Phocas (arXiv:1805.09682),
+    sharded over d: per coordinate, the mean of the P-b values nearest to a robust
+    centre c — the median (center="median") or the b-trimmed mean
+    (center="trimmed_mean").
+
+    Same shape as TrimmedMeanAggregator: all_to_all, ONE kernel on the local shard
+    (ops.column_mean_around: per-column sort, centre, window, mean), all_gather — no
+    cross-shard allreduce, no host read.
+
+    Only the b values farthest from c are dropped, on whichever side they lie, so a
+    one-sided adversary costs no honest value on the quiet side (trimmed mean drops b
+    per end regardless).  Guarantee, with at most b corrupted workers and P > 2b: c
+    lies inside the honest workers' [min, max] and |out - c| <= max over honest h of
+    |h - c| (the radius guarantee), NaN/Inf inputs included — a NaN sorts as +inf and
+    at most b non-finite values never enter the window.  Unlike the median and the
+    trimmed mean, the output is NOT confined to the honest [min, max] per coordinate:
+    a corrupted value just outside that range can be nearer to c than a far honest
+    one.  (More than b non-finite rows can yield inf/NaN — the trainer's nan-guard
+    then skips the update.)
+    """
+
+    MAX_WORKERS = 64  # the kernel sorts a column in registers, padded to <= 64 rows
+
+    def __init__(self, comm, space, num_workers: int, b: int, center: str = "median"):
+        super().__init__(comm, space)
+        if center not in ("median", "trimmed_mean"):
+            raise ValueError(f"center must be 'median' or 'trimmed_mean', got {center!r}")
+        self.num_workers = num_workers
+        self.b = b
+        self.center = center
+        self.name = "meamed" if center == "median" else "phocas"
+        if num_workers > self.MAX_WORKERS:
+            # CPU-side config check: fail at construction, not at the first launch
+            raise ValueError(
+                f"MeanAroundAggregator supports at most {self.MAX_WORKERS} workers "
+                f"(got {num_workers}): the column-sort HIP kernel holds a column in registers")
+        self._bounds(num_workers)
+
+    def _bounds(self, P: int):
+        """(keep, clo, chi) for P received rows (computed per call: the survivor world
+        after a rank failure has fewer rows)."""
+        if self.b < 0:
+            raise ValueError(f"b must be >= 0, got {self.b}")
+        if 2 * self.b >= P:
+            raise ValueError(
+                f"{self.name} with b={self.b} needs more than {2 * self.b} workers, got {P}")
+        if self.center == "median":
+            return P - self.b, (P - 1) // 2, P // 2 + 1
+        return P - self.b, self.b, P - self.b
+
+    def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
+        recv = self.exchanged(payload)  # (P, shard)
+        keep, clo, chi = self._bounds(recv.shape[0])
+        ops.column_mean_around(recv, keep, clo, chi, self._shard_out)
         self.comm.all_gather_shard(self._shard_out, self._out)
         return self._out
 

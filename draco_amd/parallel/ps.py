@@ -33,6 +33,7 @@ from .aggregators import (
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
+    MeanAroundAggregator,
     TrimmedMeanAggregator,
     VoteAggregator,
 )
@@ -136,9 +137,13 @@ class Master(_PSBase):
             elif cfg.mode == "trimmed_mean":
                 self.agg = TrimmedMeanAggregator(local, self.space, num_workers=self.P,
                                                  trim=cfg.worker_fail)
+            elif cfg.mode in ("meamed", "phocas"):
+                self.agg = MeanAroundAggregator(
+                    local, self.space, num_workers=self.P, b=cfg.worker_fail,
+                    center="median" if cfg.mode == "meamed" else "trimmed_mean")
             else:
                 raise ValueError("baseline approach supports modes normal/geometric_median/krum/"
-                                 f"median/trimmed_mean, got {cfg.mode!r}")
+                                 f"median/trimmed_mean/meamed/phocas, got {cfg.mode!r}")
         elif cfg.approach == "maj_vote":
             r = cfg.group_size
             if self.P % r != 0:

@@ -36,6 +36,7 @@ from .aggregators import (
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
+    MeanAroundAggregator,
     TrimmedMeanAggregator,
     VoteAggregator,
 )
@@ -259,8 +260,13 @@ class Trainer:
             # trim = the tolerated adversary count, as Krum takes s = worker_fail
             return TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers,
                                          trim=cfg.worker_fail)
+        if cfg.mode in ("meamed", "phocas"):
+            # b = the tolerated adversary count; the centre is the median / b-trimmed mean
+            return MeanAroundAggregator(
+                self.comm, self.space, num_workers=num_workers, b=cfg.worker_fail,
+                center="median" if cfg.mode == "meamed" else "trimmed_mean")
         raise ValueError("baseline approach supports modes normal/geometric_median/krum/"
-                         f"median/trimmed_mean, got {cfg.mode!r}")
+                         f"median/trimmed_mean/meamed/phocas, got {cfg.mode!r}")
 
     def _setup_decode(self) -> None:
         """Build the aggregator + comm-layout buffers for the CURRENT communicator

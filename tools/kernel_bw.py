@@ -94,6 +94,56 @@ def main():
     report("column_trimmed_mean (median)", ms, B + 4 * d)
     ms = t_ms(lambda: ops.column_trimmed_mean(x, 1, 23, out))
     report("column_trimmed_mean (b=1)", ms, B + 4 * d)
+    ms = t_ms(lambda: ops.column_mean_around(x, 23, 11, 13, out))
+    report("column_mean_around (meamed b=1)", ms, B + 4 * d)
+    ms = t_ms(lambda: ops.column_mean_around(x, 23, 1, 23, out))
+    report("column_mean_around (phocas b=1)", ms, B + 4 * d)
+
+
+def mean_around_compare(rounds=3):
+    """column_mean_around (mean around median / Phocas) on the same shape as its
+    yardsticks: combine_rows (same bytes read and written: the streaming ceiling),
+    column_trimmed_mean (the same load + register sort without the window step) and
+    the torch route to the same result (fallback.column_mean_around on GPU tensors:
+    sort, compare, gather).  The arms alternate inside each round; min-max over the
+    rounds is printed per arm."""
+    from draco_amd.ops import fallback as fb
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    rows = 24
+    x = torch.randn(rows, d, device=DEV)
+    out = torch.empty(d, device=DEV)
+    ref = torch.empty(d, device=DEV)
+    B = 4 * rows * d + 4 * d
+    idx = torch.arange(rows, device=DEV)
+    w = torch.randn(rows, device=DEV)
+    arms = [
+        ("combine_rows (24 rows)", lambda: ops.combine_rows(x, idx, w, out), {}),
+        ("column_trimmed_mean (b=1)", lambda: ops.column_trimmed_mean(x, 1, 23, out), {}),
+        ("column_mean_around (meamed b=1)", lambda: ops.column_mean_around(x, 23, 11, 13, out), {}),
+        ("column_mean_around (meamed b=5)", lambda: ops.column_mean_around(x, 19, 11, 13, out), {}),
+        ("column_mean_around (phocas b=1)", lambda: ops.column_mean_around(x, 23, 1, 23, out), {}),
+        ("torch route (meamed b=1)", lambda: fb.column_mean_around(x, 23, 11, 13, ref),
+         dict(iters=3, warmup=1)),
+    ]
+    # same result first (sign of zero aside): a faster kernel that computes something
+    # else is not a comparison
+    for keep, clo, chi in ((23, 11, 13), (19, 11, 13), (23, 1, 23)):
+        ops.column_mean_around(x, keep, clo, chi, out)
+        fb.column_mean_around(x, keep, clo, chi, ref)
+        torch.cuda.synchronize()
+        assert bool((out == ref).all()), (keep, clo, chi)
+    times = {name: [] for name, _, _ in arms}
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn, kw in arms:
+            ms = t_ms(fn, **kw)
+            times[name].append(ms)
+            report(name, ms, B)
+    print("# min - max over rounds")
+    for name, _, _ in arms:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
 def trimmed_mean_compare():
@@ -141,5 +191,8 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("TRIMMED_MEAN_ONLY") == "1":
         trimmed_mean_compare()
+        raise SystemExit(0)
+    if os.environ.get("MEAN_AROUND_ONLY") == "1":
+        mean_around_compare()
         raise SystemExit(0)
     main()
