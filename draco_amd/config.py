@@ -20,9 +20,11 @@ class Config:
     seed: int = 1
     network: str = "LeNet"            # LeNet|FC|ResNet18|ResNet34|ResNet50|ResNet101|ResNet152|VGG11|VGG13|VGG16|VGG19
     mode: str = "normal"              # normal|geometric_median|krum|median|trimmed_mean|meamed|phocas|
-                                      # maj_vote|cyclic (aggregation rule; trimmed_mean drops
-                                      # worker_fail per end; meamed/phocas keep the P-worker_fail
-                                      # values nearest the median / the worker_fail-trimmed mean)
+                                      # multi_krum|bulyan|maj_vote|cyclic (aggregation rule;
+                                      # trimmed_mean drops worker_fail per end; meamed/phocas keep
+                                      # the P-worker_fail values nearest the median / the
+                                      # worker_fail-trimmed mean; multi_krum/bulyan take
+                                      # f = worker_fail and need P >= 2f+3 / 4f+3 workers)
     dataset: str = "MNIST"            # MNIST|Cifar10|ImageNetSynthetic
     comm_type: str = "Bcast"          # accepted for parity; collectives are always fused (README.md:111)
     err_mode: str = "rev_grad"        # rev_grad|constant|random|gauss|none

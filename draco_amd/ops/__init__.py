@@ -30,6 +30,7 @@ __all__ = [
     "segment_gram",
     "column_trimmed_mean",
     "column_mean_around",
+    "segment_mean_around",
     "available",
 ]
 
@@ -222,3 +223,17 @@ def column_mean_around(x, keep, clo, chi, out):
         ext.column_mean_around(x, int(keep), int(clo), int(chi), out)
         return
     fallback.column_mean_around(x, int(keep), int(clo), int(chi), out)
+
+
+def segment_mean_around(x, sel, seg, keep, clo, chi, out):
+    """out[j] = column_mean_around over the T rows sel[l] of x for column j of segment l
+    (seg: (L+1,) local bounds), +0.0 outside [seg[0], seg[L]): the Multi-Krum (keep=T,
+    clo=0, chi=T) and Bulyan (keep=T-2f, median centre) decode over a per-segment Krum
+    selection.  Unselected rows are never read; sel is clamped into [0, P).  Definition:
+    fallback.segment_mean_around."""
+    ext = _native_for(x)
+    if ext is not None:
+        ext.segment_mean_around(x, sel.to(x.device), seg.to(x.device), int(keep), int(clo),
+                                int(chi), out)
+        return
+    fallback.segment_mean_around(x, sel, seg, int(keep), int(clo), int(chi), out)

@@ -6,10 +6,11 @@
 // flat gradient space (d up to ~10^7 fp32 per model replica), so the design rules are
 // the memory ones from the CDNA4 guide: 256-thread blocks (4 waves of 64), float4
 // (16 B/lane) vectorized access, grid-stride loops capped at ~2048 blocks, wave-level
-// __shfl reductions (wave = 64 lanes on CDNA4, not 32).  The exceptions are the two
+// __shfl reductions (wave = 64 lanes on CDNA4, not 32).  The exceptions are the three
 // column-sort kernels at the end (k_col_trimmed_mean: median / trimmed mean;
-// k_col_mean_around: mean around median / Phocas), which sort each column in registers
-// and are VALU-heavy.
+// k_col_mean_around: mean around median / Phocas; k_seg_mean_around: Multi-Krum /
+// Bulyan over per-segment row selections), which sort each column in registers and are
+// VALU-heavy.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -915,13 +916,48 @@ void column_trimmed_mean(torch::Tensor x, long lo, long hi, torch::Tensor out) {
 // conditions, registers only.  The window is then summed ascending with a per-lane
 // select between acc and acc + s[r] (never "+ 0", which would turn a -0 result into
 // +0), so the result is bit-identical to the CPU fallback.
+// Steps 2-4 on a sorted column (centre, window start, window mean), shared by
+// k_col_mean_around and k_seg_mean_around; P is the number of real rows in s[0..N).
+template <int N>
+__device__ __forceinline__ float mean_around_sorted(const float (&s)[N], int P, int keep, int clo,
+                                                    int chi, float ccnt, float kcnt) {
+  const int b = P - keep;
+  float c = -0.f;
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+    if (r >= clo && r < chi) c += s[r];
+  c = c / ccnt;
+  // t[j] = s[j + keep] (+inf past the end: never compared, since j + keep < P for j < b)
+  float t[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) t[r] = s[r];
+#pragma unroll
+  for (int q = 0; (1 << q) <= N; ++q) {
+    if (keep & (1 << q)) {
+#pragma unroll
+      for (int r = 0; r < N; ++r) t[r] = (r + (1 << q) < N) ? t[r + (1 << q)] : INFINITY;
+    }
+  }
+  int w = 0;
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if (j < b) w += ((c - s[j]) > (t[j] - c)) ? 1 : 0;
+  const int wend = w + keep;
+  float acc = -0.f;
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    float nxt = acc + s[r];
+    acc = (r >= w && r < wend) ? nxt : acc;
+  }
+  return acc / kcnt;
+}
+
 template <int N>
 __global__ void __launch_bounds__(NTHREADS)
 k_col_mean_around(const float *__restrict__ x, int P, int keep, int clo, int chi,
                   float ccnt, float kcnt, float *__restrict__ out, long d, long stride) {
   long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
   long gstride = gridDim.x * (long)blockDim.x;
-  const int b = P - keep;
   for (; i < d; i += gstride) {
     float s[N];
 #pragma unroll
@@ -934,34 +970,7 @@ k_col_mean_around(const float *__restrict__ x, int P, int keep, int clo, int chi
       s[p] = v;
     }
     sort_columns(s, std::make_integer_sequence<int, kMergeExchange<N>.n>{});
-    float c = -0.f;
-#pragma unroll
-    for (int r = 0; r < N; ++r)
-      if (r >= clo && r < chi) c += s[r];
-    c = c / ccnt;
-    // t[j] = s[j + keep] (+inf past the end: never compared, since j + keep < P for j < b)
-    float t[N];
-#pragma unroll
-    for (int r = 0; r < N; ++r) t[r] = s[r];
-#pragma unroll
-    for (int q = 0; (1 << q) <= N; ++q) {
-      if (keep & (1 << q)) {
-#pragma unroll
-        for (int r = 0; r < N; ++r) t[r] = (r + (1 << q) < N) ? t[r + (1 << q)] : INFINITY;
-      }
-    }
-    int w = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-      if (j < b) w += ((c - s[j]) > (t[j] - c)) ? 1 : 0;
-    const int wend = w + keep;
-    float acc = -0.f;
-#pragma unroll
-    for (int r = 0; r < N; ++r) {
-      float nxt = acc + s[r];
-      acc = (r >= w && r < wend) ? nxt : acc;
-    }
-    out[i] = acc / kcnt;
+    out[i] = mean_around_sorted(s, P, keep, clo, chi, ccnt, kcnt);
   }
 }
 
@@ -999,6 +1008,139 @@ void column_mean_around(torch::Tensor x, long keep, long clo, long chi, torch::T
 #undef LAUNCH_CMA
 }
 
+// --------------------------------------------------------------------------- segment mean around
+// Multi-Krum / Bulyan decode (arXiv:1703.02757 §4, arXiv:1802.07927): the Krum
+// selection keeps T of the P rows PER SEGMENT (parameter tensor), and column j of
+// segment l is k_col_mean_around's arithmetic over the T values x[sel[l][k]][j] —
+// Multi-Krum: keep = T (plain mean); Bulyan: median centre, keep = T - 2f.
+//
+// Same layout as k_col_mean_around (one column per lane, grid cap, +inf padding to N,
+// register sort, mean_around_sorted); new is where the rows come from.  Per column the
+// segment is found by k_seg_wmean's binary search over the bounds staged in LDS
+// ((L+1) longs, checked against the LDS limit on the host).  The (L, T) index table is
+// NOT staged: L*T*8 bytes has no bound the host could promise (160 tensors x 64 rows is
+// 80 KiB, which would also cost occupancy), it is a few KiB that every block re-reads,
+// so it stays cache-resident and is read from global memory.  The register array s[] is
+// still indexed by compile-time k only; the table is what is read at a run-time address.
+// Every lane reads the table at its own segment's row (the lanes of a wave inside one
+// segment read one address: a broadcast), so a wave that straddles a boundary simply
+// gathers different rows per lane.  An unselected row is never read: a NaN there cannot
+// reach the output (0/1 weights in k_seg_wmean could not promise that, fmaf(0, NaN, acc)
+// is NaN).
+//
+// The gather loop has NO branch on k < T: a load behind a (wave-uniform) branch is
+// waited for before the next branch, which chains the T row reads one latency after the
+// other.  Padding slots k >= T re-read table entry T-1 — in bounds, the line already in
+// cache — and are replaced by +inf in a select, so the N index loads and then the N row
+// loads are in flight together.  Measured at d = 11.2M, 62 segments (stand-alone timing
+// of both forms, equal outputs): T=22 611 -> 454 us, T=13 367 -> 240 us, T=33 (15
+// padding slots) 1396 -> 1112 us.
+//
+// Every index read from the table is clamped into [0, P): bad sel contents give a
+// wrong row, never an out-of-bounds read (the fallback clamps the same way).  The table
+// address itself is in bounds for any seg contents, since the search result is in
+// [0, L) and the slot in [0, T).  Columns outside [seg[0], seg[L]) get +0.0, so every
+// element of out is written.
+template <int N>
+__device__ __forceinline__ void gather_column(float (&s)[N], const float *__restrict__ x,
+                                              const long *__restrict__ row, int T, int P,
+                                              long stride, long i) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    long r = row[k < T ? k : T - 1];
+    r = r < 0 ? 0 : (r >= P ? (long)P - 1 : r);
+    float v = x[r * stride + i];
+    s[k] = (k < T && v == v) ? v : INFINITY;
+  }
+}
+
+template <int N>
+__global__ void __launch_bounds__(NTHREADS)
+k_seg_mean_around(const float *__restrict__ x, const long *__restrict__ sel,
+                  const long *__restrict__ seg, int L, int T, int P, int keep, int clo,
+                  int chi, float ccnt, float kcnt, float *__restrict__ out, long d,
+                  long stride) {
+  extern __shared__ long s_seg[];
+  for (int i = threadIdx.x; i <= L; i += blockDim.x) s_seg[i] = seg[i];
+  __syncthreads();
+  long gstride = gridDim.x * (long)blockDim.x;
+  // base-indexed loop with a per-lane `valid` instead of `continue`: the sort stays in
+  // one block of straight-line code that every lane of the wave runs (a lane outside
+  // the segments sorts +inf and stores 0).  The form with an early `continue` per lane
+  // compiles to a similar instruction mix but measured 711 us against 454 us at T=22
+  // (266 against 240 us at T=13).
+  for (long base = blockIdx.x * (long)blockDim.x; base < d; base += gstride) {
+    long i = base + threadIdx.x;
+    bool valid = (i < d) && i >= s_seg[0] && i < s_seg[L];  // false for all i when L = 0
+    int lo = 0;
+    if (valid) {
+      // binary search: segment lo with seg[lo] <= i < seg[lo+1]
+      int hi = L - 1;
+      while (lo < hi) {
+        int mid = (lo + hi + 1) >> 1;
+        if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
+      }
+    }
+    float s[N];
+    if (valid) {
+      gather_column(s, x, sel + (long)lo * T, T, P, stride, i);
+    } else {
+#pragma unroll
+      for (int k = 0; k < N; ++k) s[k] = INFINITY;  // result unused
+    }
+    sort_columns(s, std::make_integer_sequence<int, kMergeExchange<N>.n>{});
+    float r = mean_around_sorted(s, T, keep, clo, chi, ccnt, kcnt);
+    if (i < d) out[i] = valid ? r : 0.f;
+  }
+}
+
+void segment_mean_around(torch::Tensor x, torch::Tensor sel, torch::Tensor seg, long keep,
+                         long clo, long chi, torch::Tensor out) {
+  CHECK_IN(x); CHECK_IDX(sel); CHECK_IDX(seg); CHECK_IN(out);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 && out.scalar_type() == torch::kFloat32,
+              "segment_mean_around: x and out must be fp32");
+  TORCH_CHECK(x.dim() == 2, "segment_mean_around: x must be 2D");
+  TORCH_CHECK(sel.dim() == 2, "segment_mean_around: sel must be 2D (L, T)");
+  TORCH_CHECK(seg.dim() == 1 && seg.numel() >= 1,
+              "segment_mean_around: seg must be 1D with L+1 >= 1 bounds");
+  long P = x.size(0), d = x.size(1), T = sel.size(1);
+  long L = seg.numel() - 1;
+  TORCH_CHECK(sel.size(0) == L, "segment_mean_around: sel must have one row per segment, got ",
+              sel.size(0), " rows for L=", L);
+  TORCH_CHECK(T >= 1 && T <= 64, "segment_mean_around kernel supports 1 <= T <= 64, got ", T);
+  TORCH_CHECK(T <= P, "segment_mean_around: need T <= P, got T=", T, " P=", P);
+  TORCH_CHECK(1 <= keep && keep <= T,
+              "segment_mean_around: need 1 <= keep <= T, got keep=", keep, " T=", T);
+  TORCH_CHECK(0 <= clo && clo < chi && chi <= T,
+              "segment_mean_around: need 0 <= clo < chi <= T, got clo=", clo, " chi=", chi,
+              " T=", T);
+  TORCH_CHECK(out.numel() == d, "segment_mean_around: out must have the length of a row of x");
+  TORCH_CHECK(d % 4 == 0, "segment_mean_around: row length must be a multiple of 4");
+  size_t smem = (size_t)(L + 1) * sizeof(long);
+  TORCH_CHECK(smem <= 64 * 1024, "segment_mean_around: ", L,
+              " segment bounds do not fit the 64 KiB of LDS a block may take");
+  if (d == 0) return;
+  dim3 grid(n_blocks(d, NTHREADS));
+  hipStream_t s = cur_stream();
+  const float *xp = x.data_ptr<float>();
+  const long *sp = sel.data_ptr<long>();
+  const long *gp = seg.data_ptr<long>();
+  float *op = out.data_ptr<float>();
+  float ccnt = (float)(chi - clo), kcnt = (float)keep;
+#define LAUNCH_SMA(N) \
+  hipLaunchKernelGGL((k_seg_mean_around<N>), grid, dim3(NTHREADS), smem, s, xp, sp, gp, (int)L, \
+                     (int)T, (int)P, (int)keep, (int)clo, (int)chi, ccnt, kcnt, op, d, d)
+  if (T <= 4) LAUNCH_SMA(4);
+  else if (T <= 8) LAUNCH_SMA(8);
+  else if (T <= 12) LAUNCH_SMA(12);
+  else if (T <= 16) LAUNCH_SMA(16);
+  else if (T <= 24) LAUNCH_SMA(24);
+  else if (T <= 32) LAUNCH_SMA(32);
+  else if (T <= 48) LAUNCH_SMA(48);
+  else LAUNCH_SMA(64);
+#undef LAUNCH_SMA
+}
+
 // --------------------------------------------------------------------------- module
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd_step", &fused_sgd_step);
@@ -1021,4 +1163,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segment_gram", &segment_gram);
   m.def("column_trimmed_mean", &column_trimmed_mean);
   m.def("column_mean_around", &column_mean_around);
+  m.def("segment_mean_around", &segment_mean_around);
 }

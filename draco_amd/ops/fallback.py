@@ -384,6 +384,47 @@ def column_mean_around(x: torch.Tensor, keep: int, clo: int, chi: int,
     torch.div(acc, torch.full_like(acc, float(keep)), out=out)
 
 
+# --------------------------------------------------------------------- segment mean around
+@torch.no_grad()
+def segment_mean_around(x: torch.Tensor, sel: torch.Tensor, seg: torch.Tensor, keep: int,
+                        clo: int, chi: int, out: torch.Tensor) -> None:
+    """column_mean_around over a per-segment row selection (Multi-Krum / Bulyan decode).
+
+    x: (P, d) fp32; sel: (L, T) int64 row indices into x, distinct within a row;
+    seg: (L+1,) non-decreasing local segment bounds (zero-length segments, seg[0] > 0
+    and seg[L] < d are legal); out: (d,).  1 <= T <= P; keep, clo, chi relative to T.
+    For column j of segment l, out[j] = column_mean_around of the T values
+    x[sel[l, k], j] (the order of sel[l] cannot matter: they are sorted); columns
+    outside [seg[0], seg[L]) get +0.0, so every element of out is written.  A row that
+    is not selected for a segment is never read there: a NaN in it cannot reach out.
+    Indices are clamped into [0, P), as in the HIP kernel, which performs the same fp32
+    operations in the same order: bit-identical.
+    """
+    P, d = x.shape
+    L = seg.numel() - 1
+    if sel.dim() != 2 or sel.shape[0] != L:
+        raise ValueError(f"segment_mean_around: sel must be (L, T) with L={L}, "
+                         f"got {tuple(sel.shape)}")
+    T = sel.shape[1]
+    if not 1 <= T <= P:
+        raise ValueError(f"segment_mean_around needs 1 <= T <= P, got T={T} P={P}")
+    if not 1 <= keep <= T:
+        raise ValueError(f"segment_mean_around needs 1 <= keep <= T, got keep={keep} T={T}")
+    if not 0 <= clo < chi <= T:
+        raise ValueError(
+            f"segment_mean_around needs 0 <= clo < chi <= T, got clo={clo} chi={chi} T={T}")
+    if out.numel() != d:
+        raise ValueError("segment_mean_around: out must have the length of a row of x")
+    if d == 0:
+        return
+    out.zero_()
+    rows = sel.clamp(0, P - 1)
+    for l in range(L):
+        lo, hi = int(seg[l]), int(seg[l + 1])
+        if hi > lo:
+            column_mean_around(x[rows[l]][:, lo:hi], keep, clo, chi, out[lo:hi])
+
+
 # --------------------------------------------------------------------- dtype cast
 @torch.no_grad()
 def cast_to_bf16(x: torch.Tensor, out: torch.Tensor) -> None:

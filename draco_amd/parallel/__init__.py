@@ -1,9 +1,11 @@
 from .aggregators import (
+    BulyanAggregator,
     CyclicAggregator,
     GeoMedianAggregator,
     KrumAggregator,
     MeanAggregator,
     MeanAroundAggregator,
+    MultiKrumAggregator,
     TrimmedMeanAggregator,
     VoteAggregator,
 )
@@ -19,6 +21,8 @@ __all__ = [
     "VoteAggregator",
     "GeoMedianAggregator",
     "KrumAggregator",
+    "MultiKrumAggregator",
+    "BulyanAggregator",
     "TrimmedMeanAggregator",
     "MeanAroundAggregator",
     "CyclicAggregator",

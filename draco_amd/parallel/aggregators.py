@@ -10,6 +10,8 @@ all_gather of the decoded shard.  Reference semantics per policy:
   maj_vote     rep_master.py:141-168                (group-wise Boyer-Moore vote)
   geo_median   baseline_master.py:271-276           (per-layer Weiszfeld)
   krum         baseline_master.py:278-296           (per-layer Krum selection)
+  multi_krum   (not in the reference) arXiv:1703.02757  (per-layer mean of the P-f best Krum scores)
+  bulyan       (not in the reference) arXiv:1802.07927  (per-layer iterated Krum, then mean around median)
   median       (not in the reference) arXiv:1803.01498  (coordinate-wise median)
   trimmed_mean (not in the reference) arXiv:1803.01498  (coordinate-wise b-trimmed mean)
   meamed       (not in the reference) arXiv:1802.10116  (mean of the P-b values nearest the median)
@@ -402,6 +404,78 @@ class GeoMedianAggregator(Aggregator):
         return self._out
 
 
+# ------------------------------------------------------------------ Krum-family scoring
+# Shared by KrumAggregator, MultiKrumAggregator and BulyanAggregator.  Everything works
+# on the allreduced (L, P, P) Gram in fp64 ON DEVICE with no host read (CDNA4 fp64 is
+# strong and the matrices are tiny); every rank holds the identical allreduced bits,
+# so every rank arrives at the identical selection.
+def gram_sq_distances(gram: torch.Tensor) -> torch.Tensor:
+    """(L, P, P) Gram -> (L, P, P) fp64 squared distances |x_a|^2 + |x_b|^2 - 2<x_a, x_b>,
+    clamped at 0, +inf on the diagonal (a row is not its own neighbour)."""
+    g = gram.double()
+    P = g.shape[1]
+    diag = g.diagonal(dim1=1, dim2=2)  # (L, P)
+    d2 = (diag.unsqueeze(2) + diag.unsqueeze(1) - 2.0 * g).clamp_(min=0.0)
+    eye = torch.eye(P, dtype=torch.bool, device=d2.device)
+    d2.masked_fill_(eye, float("inf"))
+    return d2
+
+
+def krum_scores(d2: torch.Tensor, keep: int) -> torch.Tensor:
+    """(L, P) Krum scores: per row, the sum of its `keep` smallest distances."""
+    vals, _ = torch.sort(d2, dim=2)
+    return vals[:, :, :keep].sum(dim=2)
+
+
+def selection_distances(gram: torch.Tensor) -> torch.Tensor:
+    """gram_sq_distances with every non-finite distance counted as +inf: a row with a
+    NaN/Inf element (or one whose squared norm overflows fp32) has a non-finite Gram
+    row, and argmin over a NaN score would PICK that row.  (KrumAggregator keeps the
+    plain distances: its results are not this change's to alter.)  The result is made
+    exactly symmetric (the HIP Gram is by construction, a BLAS one need not be): at
+    keep = 1 two rows that are each other's nearest neighbour then tie exactly, and the
+    lower index wins on every device."""
+    inf = float("inf")
+    d2 = torch.nan_to_num(gram_sq_distances(gram), nan=inf, posinf=inf, neginf=inf)
+    return torch.minimum(d2, d2.transpose(1, 2))
+
+
+def select_multi_krum(gram: torch.Tensor, f: int, m: int) -> torch.Tensor:
+    """One-shot selection (arXiv:1703.02757 §4): (L, m) int64, per segment the m rows
+    of lowest Krum score (sum of the max(P-f-2, 1) smallest distances to the others),
+    ties to the lower row index, in score order."""
+    d2 = selection_distances(gram)
+    P = d2.shape[1]
+    scores = krum_scores(d2, max(P - f - 2, 1))
+    _, order = torch.sort(scores, dim=1, stable=True)
+    return order[:, :m].contiguous()
+
+
+def select_bulyan(gram: torch.Tensor, f: int, theta: int) -> torch.Tensor:
+    """Iterative selection (arXiv:1802.07927): (L, theta) int64 distinct rows per
+    segment.  theta times: among the n' rows remaining, score = sum of the
+    max(n'-f-2, 1) smallest distances to the other REMAINING rows; the lowest score
+    wins (lower index on ties) and leaves the pool.  A removed row is never chosen
+    again, even when every remaining score is +inf (f = 0 on the last pick)."""
+    d2 = selection_distances(gram)
+    L, P = d2.shape[0], d2.shape[1]
+    inf = float("inf")
+    remaining = torch.ones(L, P, dtype=torch.bool, device=d2.device)
+    rows = torch.arange(L, device=d2.device)
+    picks = []
+    for t in range(theta):
+        n_rem = P - t
+        pair = remaining.unsqueeze(2) & remaining.unsqueeze(1)
+        scores = krum_scores(d2.masked_fill(~pair, inf), max(n_rem - f - 2, 1))
+        scores = scores.masked_fill(~remaining, inf)
+        best = scores.min(dim=1, keepdim=True).values
+        # first remaining row at the best score (argmax of a 0/1 tensor: first maximum)
+        pick = (remaining & (scores == best)).to(torch.int32).argmax(dim=1)
+        picks.append(pick)
+        remaining[rows, pick] = False
+    return torch.stack(picks, dim=1)
+
+
 class KrumAggregator(Aggregator):
     """Per-layer Krum selection (arXiv:1703.02757), sharded over d.
 
@@ -435,19 +509,12 @@ class KrumAggregator(Aggregator):
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
         recv = self.exchanged(payload)  # (P, shard)
-        P = recv.shape[0]
         gram = ops.segment_gram(recv, self.local_seg)  # (L, P, P)
         self.comm.all_reduce(gram)
         # selection entirely ON DEVICE (fp64 — CDNA4 fp64 is strong and the matrix
         # is tiny; identical allreduced Gram -> identical winners on every rank)
-        g = gram.double()
-        diag = g.diagonal(dim1=1, dim2=2)  # (L, P)
-        d2 = (diag.unsqueeze(2) + diag.unsqueeze(1) - 2.0 * g).clamp_(min=0.0)
-        eye = torch.eye(P, dtype=torch.bool, device=d2.device)
-        d2.masked_fill_(eye, float("inf"))
-        keep = max(self.num_workers - self.s - 2, 1)
-        vals, _ = torch.sort(d2, dim=2)
-        scores = vals[:, :, :keep].sum(dim=2)  # (L, P)
+        d2 = gram_sq_distances(gram)
+        scores = krum_scores(d2, max(self.num_workers - self.s - 2, 1))  # (L, P)
         winners = scores.argmin(dim=1)  # (L,)
         out = self._shard_out
         if self._tail > 0:
@@ -457,6 +524,140 @@ class KrumAggregator(Aggregator):
             out[self._tail:] = 0.0
         self.comm.all_gather_shard(out, self._out)
         return self._out
+
+
+class _KrumSelectAggregator(Aggregator):
+    """Shared pipeline of Multi-Krum and Bulyan: all_to_all, per-segment Gram on the
+    local shard, ONE (L, P, P) allreduce, on-device selection of T rows per segment
+    (no host read), ONE kernel (ops.segment_mean_around gathers each column's rows
+    through the per-segment index table), all_gather.  last_sel keeps the (L, T)
+    selection of the latest call, on device."""
+
+    MAX_WORKERS = 32  # the segment-Gram HIP kernel stages a (P, chunk) LDS tile for P <= 32
+
+    def __init__(self, comm, space, num_workers: int, f: int):
+        super().__init__(comm, space)
+        self.num_workers = num_workers
+        self.f = f
+        self.last_sel = None
+        self._plan(num_workers)  # CPU-side config check: fail at construction
+
+    def _plan(self, P: int):
+        raise NotImplementedError
+
+    def _check_workers(self, P: int, need: int, why: str) -> None:
+        if self.f < 0:
+            raise ValueError(f"f must be >= 0, got {self.f}")
+        if P > self.MAX_WORKERS:
+            raise ValueError(
+                f"{self.name} supports at most {self.MAX_WORKERS} workers (got {P}): "
+                "the segment-Gram HIP kernel stages a (P, chunk) LDS tile sized for P <= 32")
+        if P < need:
+            raise ValueError(
+                f"{self.name} with f={self.f} needs at least {why} = {need} workers, got {P}")
+
+    def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
+        recv = self.exchanged(payload)  # (P, shard)
+        select, keep, clo, chi = self._plan(recv.shape[0])
+        gram = ops.segment_gram(recv, self.local_seg)  # (L, P, P)
+        self.comm.all_reduce(gram)
+        sel = select(gram)  # (L, T)
+        self.last_sel = sel
+        # writes the whole shard, the zero pad tail past the last segment included
+        ops.segment_mean_around(recv, sel, self.local_seg, keep, clo, chi, self._shard_out)
+        self.comm.all_gather_shard(self._shard_out, self._out)
+        return self._out
+
+
+class MultiKrumAggregator(_KrumSelectAggregator):
+    """Per-layer Multi-Krum (arXiv:1703.02757 §4), sharded over d: the plain mean of the
+    m workers of lowest Krum score (default m = P - f), where Krum returns the single
+    best one and so gives up the variance reduction of averaging.
+
+    Score of a worker = sum of its max(P-f-2, 1) smallest squared distances to the
+    others, from the allreduced per-segment Gram; the m lowest win, ties to the lower
+    index.  Needs P >= 2f + 3 and 1 <= m <= P - f; P <= 32 (the Gram kernel's limit).
+    Bounds are recomputed per call from the received row count (survivor world).
+
+    Guarantee and its limits.  With at most f non-finite rows (any NaN/Inf element, or a
+    squared norm that overflows fp32), no non-finite row is ever selected: every distance
+    that touches such a row counts as +inf, an honest row still has at least
+    P-1-f >= max(P-f-2, 1) finite distances and so a finite score, there are at least
+    P-f >= m honest rows, and a non-finite row scores +inf.  An unselected row is never
+    read by the kernel, so its NaNs cannot reach the output (0/1 weights could not
+    promise that).  Against FINITE adversaries Multi-Krum inherits Krum's (alpha,
+    f)-resilience only in the norm sense: a selected adversarial row that sits close to
+    the honest cloud in L2 can still carry one crafted coordinate into the mean (the
+    hole Bulyan closes), and the m selected rows are averaged unweighted.
+    """
+
+    name = "multi_krum"
+
+    def __init__(self, comm, space, num_workers: int, f: int, m: int | None = None):
+        self.m = m
+        super().__init__(comm, space, num_workers, f)
+
+    def _plan(self, P: int):
+        self._check_workers(P, 2 * self.f + 3, "2f + 3")
+        m = P - self.f if self.m is None else self.m
+        if not 1 <= m <= P - self.f:
+            raise ValueError(f"multi_krum needs 1 <= m <= P - f = {P - self.f}, got m={m}")
+        f = self.f
+        return (lambda gram: select_multi_krum(gram, f, m)), m, 0, m
+
+
+class BulyanAggregator(_KrumSelectAggregator):
+    """Per-layer Bulyan (arXiv:1802.07927), sharded over d: Krum iteratively selects
+    theta = P - 2f workers; then, per coordinate, the mean of the beta = theta - 2f
+    selected values nearest their median (ops.column_mean_around's rule over the
+    selected rows, median centre).
+
+    Needs P >= 4f + 3 (so beta >= 3); P <= 32 (the Gram kernel's limit).  Bounds are
+    recomputed per call from the received row count (survivor world).
+
+    Guarantee and its limits.  With at most f non-finite rows (any NaN/Inf element, or a
+    squared norm that overflows fp32), no non-finite row is ever selected: at every pick,
+    with n' >= 2f + 1 rows remaining, an honest row has at least n'-1-f >=
+    max(n'-f-2, 1) finite distances to the other remaining rows and so a finite score,
+    at least n'-f >= 1 honest rows remain, and a non-finite row scores +inf.  FINITE
+    corrupted rows can be selected — f >= 2 identical ones win the late picks, where
+    max(n'-f-2, 1) = 1 and the score is the distance to the nearest remaining row —
+    which is what the second stage is for.  With at
+    most f corrupted rows of any kind, at most f of the theta selected rows are
+    corrupted and theta > 2f, so per coordinate the median c of the selected values lies
+    inside the selected honest rows' [min, max] and |out - c| <= max over selected
+    honest h of |h - c| (column_mean_around's radius guarantee with b = 2f >= f): one
+    crafted coordinate that slipped through Krum's L2 test moves the output by at most
+    the honest spread.  As for mean-around-median, the output itself is NOT confined to
+    the honest [min, max].  Selection is per layer, so the guarantee is per layer; it
+    is the paper's only for f < (P-3)/4 corrupted workers, not beyond.
+    """
+
+    name = "bulyan"
+
+    def _plan(self, P: int):
+        self._check_workers(P, 4 * self.f + 3, "4f + 3")
+        f = self.f
+        theta = P - 2 * f
+        beta = theta - 2 * f
+        return ((lambda gram: select_bulyan(gram, f, theta)), beta, (theta - 1) // 2,
+                theta // 2 + 1)
+
+
+BASELINE_MODES = ("normal/geometric_median/krum/median/trimmed_mean/meamed/phocas/"
+                  "multi_krum/bulyan")
+
+
+def krum_select_aggregator(mode: str, comm, space, num_workers: int, f: int):
+    """mode = multi_krum | bulyan with f = worker_fail (Trainer and PS master).  These
+    two rules have a floor on the worker count (2f+3, 4f+3) that a default
+    one-worker-per-rank configuration misses, so a configuration they cannot run at is
+    reported together with the modes one can switch to."""
+    cls = MultiKrumAggregator if mode == "multi_krum" else BulyanAggregator
+    try:
+        return cls(comm, space, num_workers=num_workers, f=f)
+    except ValueError as e:
+        raise ValueError(f"{e} (baseline approach supports modes {BASELINE_MODES})") from None
 
 
 class TrimmedMeanAggregator(Aggregator):

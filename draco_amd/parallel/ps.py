@@ -29,6 +29,7 @@ from ..optim import FlatSGD
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
 from .aggregators import (
+    BASELINE_MODES,
     CyclicAggregator,
     GeoMedianAggregator,
     KrumAggregator,
@@ -36,6 +37,7 @@ from .aggregators import (
     MeanAroundAggregator,
     TrimmedMeanAggregator,
     VoteAggregator,
+    krum_select_aggregator,
 )
 from .comm import Communicator
 from .flat import FlatSpace
@@ -141,9 +143,12 @@ class Master(_PSBase):
                 self.agg = MeanAroundAggregator(
                     local, self.space, num_workers=self.P, b=cfg.worker_fail,
                     center="median" if cfg.mode == "meamed" else "trimmed_mean")
+            elif cfg.mode in ("multi_krum", "bulyan"):
+                self.agg = krum_select_aggregator(cfg.mode, local, self.space, self.P,
+                                                  cfg.worker_fail)
             else:
-                raise ValueError("baseline approach supports modes normal/geometric_median/krum/"
-                                 f"median/trimmed_mean/meamed/phocas, got {cfg.mode!r}")
+                raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, "
+                                 f"got {cfg.mode!r}")
         elif cfg.approach == "maj_vote":
             r = cfg.group_size
             if self.P % r != 0:

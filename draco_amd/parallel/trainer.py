@@ -32,6 +32,7 @@ from ..optim import FlatSGD
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
 from .aggregators import (
+    BASELINE_MODES,
     CyclicAggregator,
     GeoMedianAggregator,
     KrumAggregator,
@@ -39,6 +40,7 @@ from .aggregators import (
     MeanAroundAggregator,
     TrimmedMeanAggregator,
     VoteAggregator,
+    krum_select_aggregator,
 )
 from .comm import Communicator
 from .flat import FlatSpace
@@ -265,8 +267,11 @@ class Trainer:
             return MeanAroundAggregator(
                 self.comm, self.space, num_workers=num_workers, b=cfg.worker_fail,
                 center="median" if cfg.mode == "meamed" else "trimmed_mean")
-        raise ValueError("baseline approach supports modes normal/geometric_median/krum/"
-                         f"median/trimmed_mean/meamed/phocas, got {cfg.mode!r}")
+        if cfg.mode in ("multi_krum", "bulyan"):
+            # f = the tolerated adversary count, as Krum takes s = worker_fail
+            return krum_select_aggregator(cfg.mode, self.comm, self.space, num_workers,
+                                          cfg.worker_fail)
+        raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, got {cfg.mode!r}")
 
     def _setup_decode(self) -> None:
         """Build the aggregator + comm-layout buffers for the CURRENT communicator

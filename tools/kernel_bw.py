@@ -146,6 +146,76 @@ def mean_around_compare(rounds=3):
         print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def bulyan_compare(rounds=3, d=11_173_952):
+    """segment_mean_around (Multi-Krum / Bulyan decode: T selected rows per segment,
+    gathered through the index table) at two Bulyan shapes, against its yardsticks at
+    the same bytes: column_mean_around on a contiguous (T, d) tensor (the same sort and
+    window arithmetic without gather or segment search), combine_rows with T rows (the
+    streaming ceiling) and the torch route to the same result (per segment:
+    index_select, then one column_mean_around launch).  Results are asserted equal
+    first; the arms alternate inside each round; min-max over the rounds per arm."""
+    d = (d + 63) // 64 * 64
+    nseg = 62
+    seg_host = [int(v) // 64 * 64 for v in torch.linspace(0, d, nseg + 1).tolist()]
+    seg_host[-1] = d
+    seg = torch.tensor(seg_host, dtype=torch.int64, device=DEV)
+    out = torch.empty(d, device=DEV)
+    ref = torch.empty(d, device=DEV)
+    gen = torch.Generator().manual_seed(0)
+    times, order = {}, []
+    shapes = []
+    for P, f in ((24, 1), (23, 5)):
+        T = P - 2 * f
+        keep, clo, chi = T - 2 * f, (T - 1) // 2, T // 2 + 1
+        x = torch.randn(P, d, device=DEV)
+        xc = x[:T].contiguous()
+        sel = torch.stack([torch.randperm(P, generator=gen)[:T] for _ in range(nseg)]).to(DEV)
+        idx = torch.arange(T, device=DEV)
+        w = torch.randn(T, device=DEV)
+
+        def torch_route(x=x, sel=sel, keep=keep, clo=clo, chi=chi):
+            for l in range(nseg):
+                lo, hi = seg_host[l], seg_host[l + 1]
+                ops.column_mean_around(torch.index_select(x[:, lo:hi], 0, sel[l]), keep, clo,
+                                       chi, ref[lo:hi])
+
+        # same result first: a faster kernel that computes something else is no comparison
+        ops.segment_mean_around(x, sel, seg, keep, clo, chi, out)
+        torch_route()
+        torch.cuda.synchronize()
+        assert bool((out == ref).all()), (P, f, "gather kernel != torch route")
+        ops.segment_mean_around(x, idx.repeat(nseg, 1), seg, keep, clo, chi, out)
+        ops.column_mean_around(xc, keep, clo, chi, ref)
+        torch.cuda.synchronize()
+        assert bool((out == ref).all()), (P, f, "identity selection != contiguous kernel")
+        tag = f"P={P} f={f} T={T} keep={keep}"
+        B = 4 * T * d + 4 * d
+        shapes.append((tag, B, [
+            (f"segment_mean_around ({tag})",
+             lambda x=x, sel=sel, k=(keep, clo, chi): ops.segment_mean_around(x, sel, seg, *k, out),
+             {}),
+            (f"column_mean_around contiguous (T={T})",
+             lambda xc=xc, k=(keep, clo, chi): ops.column_mean_around(xc, *k, out), {}),
+            (f"combine_rows ({T} rows)",
+             lambda xc=xc, idx=idx, w=w: ops.combine_rows(xc, idx, w, out), {}),
+            (f"torch route: 62 x index_select+cma (T={T})", torch_route, dict(iters=5, warmup=2)),
+        ]))
+    for r in range(rounds):
+        print(f"# round {r}")
+        for tag, B, arms in shapes:
+            for name, fn, kw in arms:
+                ms = t_ms(fn, **kw)
+                if name not in times:
+                    times[name] = []
+                    order.append(name)
+                times[name].append(ms)
+                report(name, ms, B)
+    print("# min - max over rounds")
+    for name in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:46} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+
+
 def trimmed_mean_compare():
     """column_trimmed_mean vs its two yardsticks on the same shape: the torch route to
     the same result (sort along dim 0, slice, mean) and combine_rows, which reads the
@@ -194,5 +264,8 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("MEAN_AROUND_ONLY") == "1":
         mean_around_compare()
+        raise SystemExit(0)
+    if os.environ.get("BULYAN_ONLY") == "1":
+        bulyan_compare()
         raise SystemExit(0)
     main()
