@@ -68,6 +68,8 @@ class Config:
     nan_guard: bool = True        # failure detection: skip updates on non-finite decode
     gpu_timing: bool = False      # device-accurate phase spans via HIP events (metrics)
     compile: bool = False         # torch.compile the model before hipGraph capture
+    fused_norm: bool = True       # ResNet BatchNorm+add+ReLU through the fused NHWC HIP
+                                  # kernels (GPU, not under compile; ops/fused_bn.py)
     data_root: str = ""           # directory with real MNIST/CIFAR files (IDX/pickle);
                                   # empty or missing files -> deterministic synthetic data
     synthetic_task: str = "means" # means | teacher (see data/synthetic.py: teacher is

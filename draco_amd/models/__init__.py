@@ -9,6 +9,7 @@ from .resnet import (
     ResNet50ImageNet,
     ResNet101,
     ResNet152,
+    enable_fused_norm,
 )
 from .vgg import VGG
 
@@ -47,6 +48,6 @@ def build_model(network: str, dataset: str):
     raise ValueError(f"unknown network {network!r}")
 
 
-__all__ = ["build_model", "dataset_shape", "LeNet", "FC_NN", "VGG",
+__all__ = ["build_model", "dataset_shape", "enable_fused_norm", "LeNet", "FC_NN", "VGG",
            "ResNet18", "ResNet34", "ResNet50", "ResNet101", "ResNet152",
            "ResNet50ImageNet"]

@@ -10,6 +10,8 @@ shortcut rule) is the public ResNet design and is the capability being reproduce
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops import fused_bn_act
+
 
 def _conv_bn(width_in: int, width_out: int, k: int, stride: int = 1) -> nn.Sequential:
     return nn.Sequential(
@@ -25,8 +27,25 @@ def _skip_path(width_in: int, width_out: int, stride: int) -> nn.Module:
     return _conv_bn(width_in, width_out, 1, stride)
 
 
+def _conv_bn_act(seq: nn.Sequential, x, residual=None, relu=True):
+    """A _conv_bn pair with the BatchNorm, the residual add and the ReLU as one op."""
+    return fused_bn_act(seq[0](x), seq[1], residual, relu)
+
+
+def enable_fused_norm(model: nn.Module, on: bool = True) -> nn.Module:
+    """Route the BatchNorm(+add)+ReLU of every ResNet block and stem of `model` through
+    ops.fused_bn_act (native kernels for bf16 channels_last training on GPU, the plain
+    torch expression otherwise).  Off by default; parameters, buffers and state_dict
+    keys are the same either way."""
+    for m in model.modules():
+        if isinstance(m, (BasicBlock, Bottleneck, ResNet)):
+            m.fused_norm = bool(on)
+    return model
+
+
 class BasicBlock(nn.Module):
     expansion = 1
+    fused_norm = False
 
     def __init__(self, width_in: int, width: int, stride: int = 1):
         super().__init__()
@@ -34,13 +53,22 @@ class BasicBlock(nn.Module):
         self.body2 = _conv_bn(width, width, 3)
         self.skip = _skip_path(width_in, width * self.expansion, stride)
 
+    def _skip_fused(self, x):
+        if isinstance(self.skip, nn.Identity):
+            return x
+        return _conv_bn_act(self.skip, x, relu=False)
+
     def forward(self, x):
+        if self.fused_norm:
+            out = _conv_bn_act(self.body1, x)
+            return _conv_bn_act(self.body2, out, residual=self._skip_fused(x))
         out = self.body2(F.relu(self.body1(x)))
         return F.relu(out + self.skip(x))
 
 
 class Bottleneck(nn.Module):
     expansion = 4
+    fused_norm = False
 
     def __init__(self, width_in: int, width: int, stride: int = 1):
         super().__init__()
@@ -49,7 +77,13 @@ class Bottleneck(nn.Module):
         self.body3 = _conv_bn(width, width * self.expansion, 1)
         self.skip = _skip_path(width_in, width * self.expansion, stride)
 
+    _skip_fused = BasicBlock._skip_fused
+
     def forward(self, x):
+        if self.fused_norm:
+            out = _conv_bn_act(self.body1, x)
+            out = _conv_bn_act(self.body2, out)
+            return _conv_bn_act(self.body3, out, residual=self._skip_fused(x))
         out = F.relu(self.body1(x))
         out = F.relu(self.body2(out))
         out = self.body3(out)
@@ -68,6 +102,8 @@ def _stages(block, depths):
 class ResNet(nn.Module):
     """CIFAR geometry: 3x3 stem, 4 stages at 32x32 input."""
 
+    fused_norm = False
+
     def __init__(self, block, depths, num_classes=10, in_channels=3):
         super().__init__()
         self.stem = _conv_bn(in_channels, 64, 3)
@@ -82,8 +118,13 @@ class ResNet(nn.Module):
         self.stages = nn.Sequential(*stages)
         self.fc = nn.Linear(width_in, num_classes)
 
+    def _stem(self, x):
+        if self.fused_norm:
+            return _conv_bn_act(self.stem, x)
+        return F.relu(self.stem(x))
+
     def forward(self, x):
-        out = F.relu(self.stem(x))
+        out = self._stem(x)
         out = self.stages(out)
         out = F.adaptive_avg_pool2d(out, 1).flatten(1)
         return self.fc(out)
@@ -98,7 +139,7 @@ class ResNetImageNet(ResNet):
         self.pool = nn.MaxPool2d(3, stride=2, padding=1)
 
     def forward(self, x):
-        out = self.pool(F.relu(self.stem(x)))
+        out = self.pool(self._stem(x))
         out = self.stages(out)
         out = F.adaptive_avg_pool2d(out, 1).flatten(1)
         return self.fc(out)

@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 from . import fallback
+from .fused_bn import fused_bn_act
 from .native import available, get_extension, require_extension
 
 __all__ = [
@@ -31,6 +32,7 @@ __all__ = [
     "column_trimmed_mean",
     "column_mean_around",
     "segment_mean_around",
+    "fused_bn_act",
     "available",
 ]
 

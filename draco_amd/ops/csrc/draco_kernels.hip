@@ -1142,7 +1142,10 @@ void segment_mean_around(torch::Tensor x, torch::Tensor sel, torch::Tensor seg, 
 }
 
 // --------------------------------------------------------------------------- module
+void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  register_bn_ops(m);
   m.def("fused_sgd_step", &fused_sgd_step);
   m.def("fused_adam_step", &fused_adam_step);
   m.def("inject", &inject);

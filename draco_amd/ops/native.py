@@ -32,9 +32,11 @@ def get_extension():
 def _check_stale(ext) -> None:
     import warnings
 
-    src = os.path.join(os.path.dirname(__file__), "csrc", "draco_kernels.hip")
+    csrc = os.path.join(os.path.dirname(__file__), "csrc")
     try:
-        if os.path.getmtime(src) > os.path.getmtime(ext.__file__) + 1.0:
+        built = os.path.getmtime(ext.__file__) + 1.0
+        srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hip")]
+        if any(os.path.getmtime(src) > built for src in srcs):
             warnings.warn(
                 "draco_amd._hip_ops is OLDER than its kernel source — rebuild with "
                 "`python setup.py build_ext --inplace` (stale .so gives wrong/missing ops)"

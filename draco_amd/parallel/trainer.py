@@ -27,7 +27,7 @@ from .. import ops
 from ..coding import AdversarySchedule, build_cyclic_code
 from ..config import Config
 from ..data import GlobalBatchSource, GroupBatchSource, SyntheticClassification
-from ..models import build_model
+from ..models import build_model, enable_fused_norm
 from ..optim import FlatSGD
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
@@ -77,6 +77,9 @@ class Trainer:
         torch.manual_seed(cfg.seed)
         self.model = build_model(cfg.network, cfg.dataset).to(device)
         self.model.train()
+        if cfg.fused_norm and device.type == "cuda" and not cfg.compile:
+            # dynamo must not meet the extension call: --compile keeps the torch ops
+            enable_fused_norm(self.model)
         if cfg.compile and device.type == "cuda":
             import torch._dynamo as _dynamo
 

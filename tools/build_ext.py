@@ -14,7 +14,9 @@ import sysconfig
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "draco_amd", "ops", "csrc", "draco_kernels.hip")
+CSRC = os.path.join(REPO, "draco_amd", "ops", "csrc")
+# every translation unit of the one _hip_ops extension
+SRCS = [os.path.join(CSRC, name) for name in ("draco_kernels.hip", "bn_kernels.hip")]
 
 
 def so_path() -> str:
@@ -26,7 +28,7 @@ def needs_build() -> bool:
     out = so_path()
     if not os.path.exists(out):
         return True
-    return os.path.getmtime(SRC) > os.path.getmtime(out)
+    return any(os.path.getmtime(src) > os.path.getmtime(out) for src in SRCS)
 
 
 def build(verbose: bool = True, force: bool = False) -> str:
@@ -44,7 +46,7 @@ def build(verbose: bool = True, force: bool = False) -> str:
         "-std=c++17",
         "-fPIC",
         "-shared",
-        SRC,
+        *SRCS,
         "-o", out,
         f"-I{t_inc}",
         f"-I{os.path.join(t_inc, 'torch', 'csrc', 'api', 'include')}",

@@ -255,7 +255,102 @@ def gram_compare():
     report("segment_gram rocBLAS (62 mm)", ms, B)
 
 
+def t_graph_ms(fn, reps=10, iters=20):
+    """Per-call time of `fn` replayed from a hipGraph holding `reps` calls: device time
+    without the Python and autograd launch overhead, which for a 10 us kernel is most of
+    what t_ms would see (and is not there in the trainer, which replays graphs)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(reps):
+            keep = fn()  # noqa: F841 - outputs live until the capture ends
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        g.replay()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / (iters * reps) * 1e3
+
+
+def fused_bn_compare(rounds=3):
+    """Fused BatchNorm(+residual)+ReLU forward and backward against the torch bf16 op
+    sequence they replace (F.batch_norm, add, relu and its autograd), at the four
+    ResNet-18 stage shapes of the flagship (128 images, bf16 NHWC), with and without a
+    residual.  Each arm (forward, and forward+backward) is timed as hipGraph replays
+    (t_graph_ms); the arms alternate inside each round; min-max over the rounds per arm.
+    GB/s is the MINIMUM traffic over the time: forward 2 reads of x (+1 of the residual)
+    + 1 write; backward dy, y, x read twice + dx written (with a residual the fused
+    kernels write and re-read dz instead of re-reading dy and y: the same bytes)."""
+    import torch.nn as nn
+    import torch.nn.functional as F
+
+    from draco_amd.ops import fused_bn_act
+
+    cl = torch.channels_last
+    shapes = [(128, 64, 32, 32), (128, 128, 16, 16), (128, 256, 8, 8), (128, 512, 4, 4)]
+    arms, times, numel = [], {}, {}
+    for N, C, H, W in shapes:
+        for has_res in (False, True):
+            x = (torch.randn(N, C, H, W, device=DEV) + 3).to(torch.bfloat16).contiguous(memory_format=cl)
+            res = torch.randn_like(x) if has_res else None
+            dy = torch.randn_like(x)
+            bn = nn.BatchNorm2d(C).to(DEV).train()
+            nb = x.numel() * 2
+            fwd_bytes = nb * (4 if has_res else 3)
+            bwd_bytes = nb * 7
+
+            def torch_fwd(xi, bn=bn, res=res):
+                o = bn(xi)
+                if res is not None:
+                    o = o + res
+                return F.relu(o)
+
+            def fused_fwd(xi, bn=bn, res=res):
+                return fused_bn_act(xi, bn, res, True)
+
+            tag = f"{C}x{H}x{W}{' +res' if has_res else ''}"
+            numel[tag] = x.numel()
+            for kind, fwd in (("torch", torch_fwd), ("fused", fused_fwd)):
+                xi = x.clone().requires_grad_()
+                ri = res.clone().requires_grad_() if has_res else None
+                f = (lambda fwd=fwd, xi=xi, ri=ri: fwd(xi, res=ri)) if has_res else \
+                    (lambda fwd=fwd, xi=xi: fwd(xi))
+                wrt = [xi, bn.weight, bn.bias] + ([ri] if has_res else [])
+                # forward and backward are captured TOGETHER: autograd runs a node's
+                # backward on the stream its forward ran on, so a backward whose
+                # forward happened outside the capture would launch outside it too
+                fb = lambda f=f, wrt=wrt, dy=dy: torch.autograd.grad(f(), wrt, dy)
+                arms.append((f"{kind} fwd {tag}", f, fwd_bytes))
+                arms.append((f"{kind} fwd+bwd {tag}", fb, fwd_bytes + bwd_bytes))
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn, nbytes in arms:
+            ms = t_graph_ms(fn)
+            times.setdefault(name, []).append(ms)
+            report(name, ms, nbytes)
+    print("# min - max over rounds (us), GB/s at the min")
+    for (name, _, nbytes) in arms:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
+    print("# backward alone = (fwd+bwd) - fwd at the min, against its 7 tensor passes")
+    for (name, _, _) in arms:
+        if " fwd+bwd " in name:
+            us = (min(times[name]) - min(times[name.replace(" fwd+bwd ", " fwd ")])) * 1e3
+            nbytes = numel[name.split(" fwd+bwd ")[1]] * 2 * 7
+            print(f"{name.replace(' fwd+bwd ', ' bwd '):34} {us:9.1f} us  {nbytes/us/1e3:8.1f} GB/s")
+
+
 if __name__ == "__main__":
+    if os.environ.get("FUSED_BN_ONLY") == "1":
+        fused_bn_compare()
+        raise SystemExit(0)
     if os.environ.get("GRAM_ONLY") == "1":
         gram_compare()
         raise SystemExit(0)
