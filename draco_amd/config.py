@@ -27,7 +27,10 @@ class Config:
                                       # f = worker_fail and need P >= 2f+3 / 4f+3 workers)
     dataset: str = "MNIST"            # MNIST|Cifar10|ImageNetSynthetic
     comm_type: str = "Bcast"          # accepted for parity; collectives are always fused (README.md:111)
-    err_mode: str = "rev_grad"        # rev_grad|constant|random|gauss|none
+    err_mode: str = "rev_grad"        # rev_grad|constant|random|gauss|none, computed by one worker
+                                      # from its own gradient, or the colluding alie|ipm
+                                      # (coding/collusion.py: baseline approach, colocated
+                                      # topology only; their strength is attack_param)
     approach: str = "maj_vote"        # baseline|maj_vote|cyclic
     num_aggregate: int = 5            # parity flag (unused, as in reference)
     eval_freq: int = 50
@@ -75,8 +78,29 @@ class Config:
     synthetic_task: str = "means" # means | teacher (see data/synthetic.py: teacher is
                                   # the non-saturating convergence-evidence task)
     log_dir: str = "output/logs/"
+    attack_param: float = float("nan")  # colluding err modes: z of alie (mu - z*sigma), eps of
+                                        # ipm (-eps*mu); nan = the default (alie: the paper's
+                                        # z_max, which is 0 at many small P; ipm: 0.1)
 
     def sanity(self):
+        from .coding.collusion import COLLUDING_MODES
+
+        if self.err_mode in COLLUDING_MODES:
+            what = (f"err-mode {self.err_mode!r} is a colluding mode "
+                    f"({'/'.join(COLLUDING_MODES)}): ")
+            if self.approach != "baseline":
+                raise ValueError(
+                    what + "colluding modes need --approach baseline (the coded approaches' "
+                    f"threat model is per-worker corruption), got {self.approach!r}")
+            if self.topology == "ps":
+                raise ValueError(
+                    what + "colluding modes need the colocated topology, not --topology ps")
+            if self.health_timeout > 0:
+                raise ValueError(
+                    what + "colluding modes cannot be combined with --health-timeout (the "
+                    "row-to-worker mapping of a survivor world is not built)")
+            if self.worker_fail < 1:
+                raise ValueError(what + "colluding modes need --worker-fail >= 1")
         if self.approach == "maj_vote" and self.group_size < 1:
             raise ValueError("group-size must be >= 1 for maj_vote")
         if self.approach == "cyclic" and self.worker_fail < 1:

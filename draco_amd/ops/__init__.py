@@ -15,6 +15,7 @@ __all__ = [
     "fused_sgd_step",
     "fused_adam_step",
     "inject_",
+    "collude_",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -90,6 +91,19 @@ def inject_(grad, mode, cyclic=False):
         ext.inject(grad, mode, bool(cyclic))
         return
     fallback.inject_(grad, mode, cyclic)
+
+
+def collude_(x, rows, a, b):
+    """In place on the exchanged (P, n) block: every row in `rows` (a host sequence of
+    distinct ints) becomes a*mu + b*sigma per column, mu / sigma = mean / population
+    standard deviation of the other rows.  ALIE: (1, -z); inner-product manipulation:
+    (-eps, 0).  The row set reaches the kernel as a 64-bit mask by value: no device
+    tensor, no copy.  Definition and checks: fallback.collude_."""
+    ext = _native_for(x)
+    if ext is not None:
+        ext.collude(x, [int(r) for r in rows], float(a), float(b))
+        return
+    fallback.collude_(x, rows, a, b)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

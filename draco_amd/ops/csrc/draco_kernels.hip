@@ -10,7 +10,8 @@
 // column-sort kernels at the end (k_col_trimmed_mean: median / trimmed mean;
 // k_col_mean_around: mean around median / Phocas; k_seg_mean_around: Multi-Krum /
 // Bulyan over per-segment row selections), which sort each column in registers and are
-// VALU-heavy.
+// VALU-heavy.  k_collude (colluding ALIE / inner-product adversaries) keeps a column in
+// registers as they do, four columns per lane, without the sort.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -1141,6 +1142,107 @@ void segment_mean_around(torch::Tensor x, torch::Tensor sel, torch::Tensor seg, 
 #undef LAUNCH_SMA
 }
 
+// --------------------------------------------------------------------------- collusion
+// Colluding adversaries that see the honest gradients: ALIE ("A Little Is Enough",
+// Baruch et al., arXiv:1902.06156: mu - z*sigma) and inner-product manipulation (Xie
+// et al., arXiv:1903.03936: -eps*mu).  In place on the (P, d) block every rank holds
+// after the all_to_all: per column, mu and the population sigma of the HONEST rows
+// (those whose bit is clear in `mask`), and every row whose bit is set is overwritten
+// with a*mu + b*sigma.  Honest rows are only read, Byzantine rows only written.
+//
+// Same padding as the column-sort kernels (honest values in registers indexed by
+// compile-time constants only, N the smallest padded size >= P), but each lane owns
+// FOUR adjacent columns and moves them as one 16-byte access (rows are 16-byte aligned:
+// d % 4 == 0): at one column per lane and 4 B per access this kernel, with no sort at
+// all, ran no faster than k_col_trimmed_mean (profiles/kernel_bw_collude.txt).  `mask`
+// is wave-uniform, so the row tests are scalar branches: a Byzantine row costs no load,
+// an honest row no store.  Two-pass variance (mu first, then the sum of (x - mu)^2,
+// rows in ascending order): the one-pass E[x^2] - mu^2 form cancels and can go negative
+// under the root.  SIGMA=false (b == 0, IPM) skips the second pass and the root.
+typedef float col4 __attribute__((ext_vector_type(4)));
+
+template <int N, bool SIGMA>
+__global__ void __launch_bounds__(NTHREADS)
+k_collude(float *x, int P, unsigned long long mask, float cnt, float a, float b, long d4,
+          long stride) {
+  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  long gstride = gridDim.x * (long)blockDim.x;
+  for (; i < d4; i += gstride) {
+    col4 s[N];
+    col4 sum = 0.f;
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      s[p] = 0.f;
+      if (p < P && !((mask >> p) & 1ull)) {
+        s[p] = *reinterpret_cast<const col4 *>(x + p * stride + 4 * i);
+        sum += s[p];
+      }
+    }
+    col4 mu = sum / cnt;
+    col4 v = a * mu;
+    if (SIGMA) {
+      col4 ss = 0.f;
+#pragma unroll
+      for (int p = 0; p < N; ++p)
+        if (p < P && !((mask >> p) & 1ull)) {
+          col4 dev = s[p] - mu;
+          ss += dev * dev;
+        }
+      ss = ss / cnt;
+      v.x += b * sqrtf(ss.x);
+      v.y += b * sqrtf(ss.y);
+      v.z += b * sqrtf(ss.z);
+      v.w += b * sqrtf(ss.w);
+    }
+#pragma unroll
+    for (int p = 0; p < N; ++p)
+      if (p < P && ((mask >> p) & 1ull)) *reinterpret_cast<col4 *>(x + p * stride + 4 * i) = v;
+  }
+}
+
+void collude(torch::Tensor x, std::vector<int64_t> rows, double a, double b) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32, "collude: x must be fp32");
+  TORCH_CHECK(x.dim() == 2, "collude: x must be 2D");
+  long P = x.size(0), d = x.size(1);
+  TORCH_CHECK(P >= 2 && P <= 64, "collude kernel supports 2 <= P <= 64, got ", P);
+  TORCH_CHECK(d % 4 == 0, "collude: row length must be a multiple of 4");
+  unsigned long long mask = 0;
+  for (int64_t r : rows) {
+    TORCH_CHECK(0 <= r && r < P, "collude: row ", r, " outside [0, ", P, ")");
+    unsigned long long bit = 1ull << r;
+    TORCH_CHECK(!(mask & bit), "collude: row ", r, " listed twice");
+    mask |= bit;
+  }
+  long h = P - (long)rows.size();
+  TORCH_CHECK(h >= 1, "collude: all ", P, " rows are Byzantine, need at least one honest row");
+  if (rows.empty() || d == 0) return;
+  float *xp = x.data_ptr<float>();
+  TORCH_CHECK((uintptr_t)xp % 16 == 0, "collude: x must be 16-byte aligned");
+  long d4 = d / 4;
+  dim3 grid(n_blocks(d4, NTHREADS));
+  hipStream_t s = cur_stream();
+  float cnt = (float)h, af = (float)a, bf = (float)b;
+#define LAUNCH_COL(N) \
+  do { \
+    if (bf != 0.f) \
+      hipLaunchKernelGGL((k_collude<N, true>), grid, dim3(NTHREADS), 0, s, xp, (int)P, mask, \
+                         cnt, af, bf, d4, d); \
+    else \
+      hipLaunchKernelGGL((k_collude<N, false>), grid, dim3(NTHREADS), 0, s, xp, (int)P, mask, \
+                         cnt, af, bf, d4, d); \
+  } while (0)
+  if (P <= 4) LAUNCH_COL(4);
+  else if (P <= 8) LAUNCH_COL(8);
+  else if (P <= 12) LAUNCH_COL(12);
+  else if (P <= 16) LAUNCH_COL(16);
+  else if (P <= 24) LAUNCH_COL(24);
+  else if (P <= 32) LAUNCH_COL(32);
+  else if (P <= 48) LAUNCH_COL(48);
+  else LAUNCH_COL(64);
+#undef LAUNCH_COL
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -1167,4 +1269,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("column_trimmed_mean", &column_trimmed_mean);
   m.def("column_mean_around", &column_mean_around);
   m.def("segment_mean_around", &segment_mean_around);
+  m.def("collude", &collude);
 }

@@ -106,12 +106,75 @@ def inject_(grad: torch.Tensor, mode: str, cyclic: bool = False) -> None:
         err = torch.randn_like(grad) * grad.abs().mean().clamp(min=1e-12) * 100.0
     elif mode in ("none", ""):
         return
+    elif mode in ("alie", "ipm"):
+        raise ValueError(
+            f"err mode {mode!r} is a colluding adversary: it needs every honest worker's "
+            "values and is applied to the exchanged (P, shard) block by collude_, not to "
+            "one worker's gradient")
     else:
         raise ValueError(f"unknown err mode {mode!r}")
     if cyclic:
         grad.add_(err)
     else:
         grad.copy_(err)
+
+
+@torch.no_grad()
+def collude_(x: torch.Tensor, rows, a: float, b: float) -> None:
+    """Colluding adversaries that see the honest gradients, in place: every row of x
+    listed in `rows` becomes a*mu + b*sigma per column, mu and sigma being the mean and
+    the population standard deviation (divide by h) of the h rows NOT listed.  ALIE
+    (arXiv:1902.06156) is (a, b) = (1, -z); inner-product manipulation
+    (arXiv:1903.03936) is (-eps, 0).
+
+    x: (P, n) fp32 contiguous, 2 <= P <= 64, n % 4 == 0; rows: distinct ints in [0, P),
+    at least one row left honest; empty rows (or n == 0) is a no-op.  Honest rows are
+    never written.  Per column, in fp32: the honest values are added one at a time in
+    ascending row order and divided by float32(h); then, unless b == 0, the squared
+    deviations from that mean are added in the same order, divided by float32(h), and
+    rooted (two passes: the one-pass E[x^2] - mu^2 form cancels and can go negative).
+    The HIP kernel does the same in the same order, up to FMA contraction: it agrees
+    within the rounding bound, not bit for bit.  Non-finite inputs propagate by
+    ordinary IEEE arithmetic.
+    """
+    if x.dtype != torch.float32:
+        raise ValueError(f"collude_: x must be fp32, got {x.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"collude_: x must be 2D, got {x.dim()}D")
+    if not x.is_contiguous():
+        raise ValueError("collude_: x must be contiguous")
+    P, n = x.shape
+    if not 2 <= P <= 64:
+        raise ValueError(f"collude_ supports 2 <= P <= 64, got {P}")
+    if n % 4 != 0:
+        raise ValueError(f"collude_: row length must be a multiple of 4, got {n}")
+    rows = [int(r) for r in rows]
+    for r in rows:
+        if not 0 <= r < P:
+            raise ValueError(f"collude_: row {r} outside [0, {P})")
+    if len(set(rows)) != len(rows):
+        raise ValueError(f"collude_: rows must be distinct, got {rows}")
+    byz = set(rows)
+    honest = [p for p in range(P) if p not in byz]
+    if not honest:
+        raise ValueError(f"collude_: all {P} rows are Byzantine, need at least one honest row")
+    if not rows or n == 0:
+        return
+    cnt = torch.full((n,), float(len(honest)), dtype=torch.float32, device=x.device)
+    acc = x[honest[0]].clone()
+    for p in honest[1:]:
+        acc = acc + x[p]
+    # tensor divisor: an elementwise IEEE division (never a multiply by 1/h)
+    mu = torch.div(acc, cnt)
+    val = mu * float(a)
+    if float(b) != 0.0:
+        ss = torch.zeros_like(mu)
+        for p in honest:
+            dev = x[p] - mu
+            ss = ss + dev * dev
+        val = val + torch.sqrt(torch.div(ss, cnt)) * float(b)
+    for r in rows:
+        x[r] = val
 
 
 # --------------------------------------------------------------------- vote

@@ -39,6 +39,10 @@ class Aggregator:
     """
 
     name = "base"
+    # coding.collusion.Collusion or None: colluding adversaries (alie / ipm) see the
+    # honest rows only after the exchange, so they act inside exchanged().  The trainer
+    # sets collusion.rows from the host-side schedule before every aggregate().
+    collusion = None
 
     def __init__(self, comm: Communicator, space: FlatSpace, comm_dtype=torch.float32):
         self.comm = comm
@@ -111,7 +115,17 @@ class Aggregator:
         self._started.add(row)
 
     def exchanged(self, payload: torch.Tensor) -> torch.Tensor:
-        """(rows, d_pad) payload -> (rows*world, shard) in l-major row order."""
+        """(rows, d_pad) payload -> (rows*world, shard) in l-major row order.  With a
+        collusion attached, the step's Byzantine rows of that block are overwritten
+        (ops.collude_) before the rule reads it."""
+        recv = self._exchange(payload)
+        col = self.collusion
+        if col is not None and col.rows:
+            # baseline approach: recv row l*world + src IS logical worker l*world + src
+            ops.collude_(recv, col.rows, col.a, col.b)
+        return recv
+
+    def _exchange(self, payload: torch.Tensor) -> torch.Tensor:
         rows = payload.shape[0]
         if not self.comm.distributed:
             return payload.view(rows, self.space.shard)

@@ -24,7 +24,13 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
-from ..coding import AdversarySchedule, build_cyclic_code
+from ..coding import (
+    COLLUDING_MODES,
+    AdversarySchedule,
+    Collusion,
+    build_cyclic_code,
+    collusion_coefficients,
+)
 from ..config import Config
 from ..data import GlobalBatchSource, GroupBatchSource, SyntheticClassification
 from ..models import build_model, enable_fused_norm
@@ -253,6 +259,20 @@ class Trainer:
                                        task=self.cfg.synthetic_task)
 
     def _baseline_aggregator(self, cfg: Config, num_workers: int):
+        if cfg.mode == "normal" and cfg.err_mode in COLLUDING_MODES:
+            # MeanAggregator sums inside the reduce-scatter: the honest rows are never
+            # visible together.  Under a colluding adversary the plain mean goes over
+            # the exchange path instead: the trimmed mean with nothing trimmed.
+            try:
+                agg = TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers,
+                                            trim=0)
+            except ValueError as e:
+                raise ValueError(
+                    f"{e} (mode 'normal' under the colluding err mode {cfg.err_mode!r} is "
+                    "the trim=0 mean over the exchange path, so that kernel's limit of 64 "
+                    "workers applies)") from None
+            agg.name = "mean"
+            return agg
         if cfg.mode == "normal":
             return MeanAggregator(self.comm, self.space, num_workers=num_workers)
         if cfg.mode == "geometric_median":
@@ -285,6 +305,12 @@ class Trainer:
         if self.approach == "baseline":
             self.agg = self._baseline_aggregator(cfg, num_workers=self.L * len(alive))
             self.payload = self.space.alloc_payload(self.L)
+            if cfg.err_mode in COLLUDING_MODES:
+                # colluding adversaries act on the exchanged block, inside aggregate()
+                P = self.L * len(alive)
+                a, b = collusion_coefficients(cfg.err_mode, P, min(cfg.worker_fail, P),
+                                              cfg.attack_param)
+                self.agg.collusion = Collusion(a, b)
         elif self.approach == "maj_vote":
             from ..coding import colocated_member_rows
 
@@ -452,6 +478,11 @@ class Trainer:
             raise ValueError(mode)
 
     def _inject_row(self, row: int, lo: int, hi: int) -> None:
+        if self.cfg.err_mode in COLLUDING_MODES:
+            # nothing at the send boundary (whole-row and bucketed path alike): the
+            # colluding workers need the honest rows, so the aggregator overwrites
+            # theirs after the exchange (Aggregator.exchanged)
+            return
         if self.cfg.err_mode == "within_tol":
             # worst-case TOLERANCE-RESPECTING adversary (security-model test): a
             # perturbation just inside the vote's equality ball — it passes the
@@ -665,6 +696,8 @@ class Trainer:
 
         t_comp = time.perf_counter()
         ev_comp = self._event()
+        if self.agg.collusion is not None:
+            self.agg.collusion.rows = tuple(sorted(adversaries))
         grad = self.agg.aggregate(self.payload, step)
         ev_agg = self._event()
         t_agg = time.perf_counter()

@@ -239,6 +239,56 @@ def trimmed_mean_compare():
         report(f"torch sort+mean ({name})", ms, B)
 
 
+def collude_compare(rounds=3):
+    """collude_ (colluding ALIE / inner-product adversaries: f rows of the 24 x 11.2M
+    block overwritten with a*mu + b*sigma of the others) against its two yardsticks on
+    the same shape: combine_rows with 24 rows (the same bytes with one row written) and
+    column_trimmed_mean(x, 0, 24) (the same loads plus a register sort).  collude_ reads
+    24-f rows and writes f.  The result is checked against the fp64 definition on a
+    column sample first; the arms alternate inside each round; min-max over the rounds
+    per arm."""
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    rows = 24
+    x = torch.randn(rows, d, device=DEV)
+    out = torch.empty(d, device=DEV)
+    idx = torch.arange(rows, device=DEV)
+    w = torch.randn(rows, device=DEV)
+    arms = [
+        ("combine_rows (24 rows)", lambda: ops.combine_rows(x, idx, w, out), 4 * (rows + 1) * d),
+        ("column_trimmed_mean (0, 24)", lambda: ops.column_trimmed_mean(x, 0, rows, out),
+         4 * (rows + 1) * d),
+    ]
+    for f in (1, 5):
+        byz = list(range(rows - f, rows))
+        for name, a, b in (("alie z=1.5", 1.0, -1.5), ("ipm eps=0.1", -0.1, 0.0)):
+            # same result first: a fast kernel that computes something else is no comparison
+            y = x.clone()
+            ops.collude_(y, byz, a, b)
+            H = x[: rows - f, :65536].double()
+            ref = a * H.mean(0) + b * ((H - H.mean(0)) ** 2).mean(0).sqrt()
+            tol = 8 * (abs(a) + abs(b)) * rows * 2.0 ** -24 * H.abs().amax(0)
+            for r in byz:
+                assert bool(((y[r, :65536].double() - ref).abs() <= tol).all()), (f, name, r)
+            assert bool((y[: rows - f] == x[: rows - f]).all()), (f, name)
+            del y
+            # the timed calls overwrite the last f rows of x again and again: the
+            # honest rows, the only ones read, never change
+            arms.append((f"collude_ f={f} {name}",
+                         lambda byz=byz, a=a, b=b: ops.collude_(x, byz, a, b), 4 * rows * d))
+    times = {name: [] for name, _, _ in arms}
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn, nbytes in arms:
+            ms = t_ms(fn)
+            times[name].append(ms)
+            report(name, ms, nbytes)
+    print("# min - max over rounds")
+    for name, _, _ in arms:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -359,6 +409,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("MEAN_AROUND_ONLY") == "1":
         mean_around_compare()
+        raise SystemExit(0)
+    if os.environ.get("COLLUDE_ONLY") == "1":
+        collude_compare()
         raise SystemExit(0)
     if os.environ.get("BULYAN_ONLY") == "1":
         bulyan_compare()
