@@ -20,11 +20,12 @@ class Config:
     seed: int = 1
     network: str = "LeNet"            # LeNet|FC|ResNet18|ResNet34|ResNet50|ResNet101|ResNet152|VGG11|VGG13|VGG16|VGG19
     mode: str = "normal"              # normal|geometric_median|krum|median|trimmed_mean|meamed|phocas|
-                                      # multi_krum|bulyan|maj_vote|cyclic (aggregation rule;
+                                      # multi_krum|bulyan|centered_clip|maj_vote|cyclic (aggregation rule;
                                       # trimmed_mean drops worker_fail per end; meamed/phocas keep
                                       # the P-worker_fail values nearest the median / the
                                       # worker_fail-trimmed mean; multi_krum/bulyan take
-                                      # f = worker_fail and need P >= 2f+3 / 4f+3 workers)
+                                      # f = worker_fail and need P >= 2f+3 / 4f+3 workers;
+                                      # centered_clip takes clip_tau / clip_iters, not worker_fail)
     dataset: str = "MNIST"            # MNIST|Cifar10|ImageNetSynthetic
     comm_type: str = "Bcast"          # accepted for parity; collectives are always fused (README.md:111)
     err_mode: str = "rev_grad"        # rev_grad|constant|random|gauss|none, computed by one worker
@@ -81,6 +82,10 @@ class Config:
     attack_param: float = float("nan")  # colluding err modes: z of alie (mu - z*sigma), eps of
                                         # ipm (-eps*mu); nan = the default (alie: the paper's
                                         # z_max, which is 0 at many small P; ipm: 0.1)
+    clip_tau: float = 0.0         # mode centered_clip: clipping radius; <= 0 or nan = auto (the
+                                  # lower median of the step's distances to the previous
+                                  # aggregate; see parallel/aggregators.CenteredClipAggregator)
+    clip_iters: int = 3           # mode centered_clip: clipping iterations per step (>= 1)
 
     def sanity(self):
         from .coding.collusion import COLLUDING_MODES

@@ -16,6 +16,7 @@ __all__ = [
     "fused_adam_step",
     "inject_",
     "collude_",
+    "clip_step_",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -104,6 +105,20 @@ def collude_(x, rows, a, b):
         ext.collude(x, [int(r) for r in rows], float(a), float(b))
         return
     fallback.collude_(x, rows, a, b)
+
+
+def clip_step_(x, v, w, dist=True):
+    """One centered-clipping iteration on the exchanged (P, n) block with the clip
+    weights w (P,) given, on x's device and never read on the host: in place,
+    v += sum over rows with w_i != 0 of w_i * (x_i - v); returns d2 (P,), the squared
+    distance of EVERY row to the new v (the next iteration's weights come from it), or
+    None with dist=False.  One pass over x serves both halves, and d2 is reduced in a
+    fixed order (no float atomics): two runs agree bit for bit.  Definition and checks:
+    fallback.clip_step_."""
+    ext = _native_for(x)
+    if ext is not None:
+        return ext.clip_step(x, v, w, bool(dist))
+    return fallback.clip_step_(x, v, w, dist)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

@@ -11,7 +11,8 @@
 // k_col_mean_around: mean around median / Phocas; k_seg_mean_around: Multi-Krum /
 // Bulyan over per-segment row selections), which sort each column in registers and are
 // VALU-heavy.  k_collude (colluding ALIE / inner-product adversaries) keeps a column in
-// registers as they do, four columns per lane, without the sort.
+// registers as they do, four columns per lane, without the sort; k_clip_step (centered
+// clipping) does the same and carries per-row distance accumulators on top.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -1243,6 +1244,169 @@ void collude(torch::Tensor x, std::vector<int64_t> rows, double a, double b) {
 #undef LAUNCH_COL
 }
 
+// --------------------------------------------------------------------------- centered clipping
+// One iteration of centered clipping (Karimireddy, He, Jaggi, arXiv:2012.10333) on the
+// (P, n) block: per column v += sum over rows with w[p] != 0 of w[p] * (x[p] - v), rows
+// in ascending order, and (DIST) d2[p] = sum over columns of (x[p] - v_new)^2 for EVERY
+// row, which are the distances the caller turns into the next iteration's weights.  The
+// column is read once and serves both halves from registers.
+//
+// Padding as in k_collude (N the smallest padded size >= P, compile-time indices only)
+// and its wide layout: each lane owns CW adjacent columns.  CW = 4 (16-byte accesses)
+// up to N = 32; N = 48 / 64 take CW = 2, because the N distance accumulators each lane
+// carries across its grid-stride trips come on top of the N * CW column registers
+// (profiles/kernel_bw_centered_clip.txt has the register counts).  `w` is wave-uniform:
+// the row tests are scalar branches, a row with w[p] == 0 is never read by the update
+// (not at all when !DIST), so a NaN there cannot reach v.  With every weight zero v is
+// not written.
+//
+// The distances use no float atomics and a fixed order: lane accumulators over the
+// lane's trips, xor-butterfly over the wave, the block's waves in ascending order
+// through LDS, one row of the (gridDim, P) workspace per block, and k_clip_finish sums
+// each workspace column in a fixed order.  The grid depends on n alone, so two runs on
+// the same input agree bit for bit.
+template <int CW> struct ColVec;
+template <> struct ColVec<4> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct ColVec<2> { typedef float type __attribute__((ext_vector_type(2))); };
+
+__device__ inline float col_sumsq(col4 d) {
+  return d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
+}
+__device__ inline float col_sumsq(ColVec<2>::type d) { return d.x * d.x + d.y * d.y; }
+
+template <int N, int CW, bool DIST>
+__global__ void __launch_bounds__(NTHREADS)
+k_clip_step(const float *__restrict__ x, float *__restrict__ v, const float *__restrict__ w,
+            float *__restrict__ ws, int P, long nv, long stride) {
+  typedef typename ColVec<CW>::type colv;
+  __shared__ float part[NTHREADS / WAVE][N];
+  float wr[N];
+  bool any = false;
+#pragma unroll
+  for (int p = 0; p < N; ++p) {
+    wr[p] = p < P ? w[p] : 0.f;
+    any = any || wr[p] != 0.f;
+  }
+  float acc[N];
+#pragma unroll
+  for (int p = 0; p < N; ++p) acc[p] = 0.f;
+  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  long gstride = gridDim.x * (long)blockDim.x;
+  for (; i < nv; i += gstride) {
+    colv vv = *reinterpret_cast<const colv *>(v + CW * i);
+    colv s[N];
+    colv delta = 0.f;
+    // loads first, with no use inside the row branches, so that they stay in flight
+    // together (a use per branch waits for each load in turn)
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      s[p] = 0.f;
+      if (p < P && (DIST || wr[p] != 0.f))
+        s[p] = *reinterpret_cast<const colv *>(x + p * stride + CW * i);
+    }
+#pragma unroll
+    for (int p = 0; p < N; ++p)
+      if (wr[p] != 0.f) delta += wr[p] * (s[p] - vv);  // wr[p] == 0 for p >= P
+    if (any) {
+      vv += delta;
+      *reinterpret_cast<colv *>(v + CW * i) = vv;
+    }
+    if (DIST) {
+#pragma unroll
+      for (int p = 0; p < N; ++p)
+        if (p < P) acc[p] += col_sumsq(s[p] - vv);
+    }
+  }
+  if (DIST) {
+    int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      if (p < P) {
+        float a = acc[p];
+#pragma unroll
+        for (int o = WAVE / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, WAVE);
+        if (lane == 0) part[wave][p] = a;
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < P) {
+      float a = part[0][threadIdx.x];
+#pragma unroll
+      for (int k = 1; k < NTHREADS / WAVE; ++k) a += part[k][threadIdx.x];
+      ws[blockIdx.x * (long)P + threadIdx.x] = a;
+    }
+  }
+}
+
+// d2[p] = sum over the nb workspace rows of ws[b][p]: one block per p, thread t adds
+// rows t, t + 256, ... in ascending order, then a fixed LDS tree over the 256 partials.
+__global__ void __launch_bounds__(NTHREADS)
+k_clip_finish(const float *__restrict__ ws, float *__restrict__ d2, int nb, int P) {
+  __shared__ float red[NTHREADS];
+  int p = blockIdx.x;
+  float a = 0.f;
+  for (int b = threadIdx.x; b < nb; b += NTHREADS) a += ws[b * (long)P + p];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = NTHREADS / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) d2[p] = red[0];
+}
+
+c10::optional<torch::Tensor> clip_step(torch::Tensor x, torch::Tensor v, torch::Tensor w,
+                                       bool dist) {
+  CHECK_IN(x);
+  CHECK_IN(v);
+  CHECK_IN(w);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 && v.scalar_type() == torch::kFloat32 &&
+                  w.scalar_type() == torch::kFloat32,
+              "clip_step: x, v and w must be fp32");
+  TORCH_CHECK(x.dim() == 2, "clip_step: x must be 2D");
+  long P = x.size(0), n = x.size(1);
+  TORCH_CHECK(P >= 1 && P <= 64, "clip_step kernel supports 1 <= P <= 64, got ", P);
+  TORCH_CHECK(n % 4 == 0, "clip_step: row length must be a multiple of 4");
+  TORCH_CHECK(v.dim() == 1 && v.size(0) == n, "clip_step: v must have shape (", n, ",)");
+  TORCH_CHECK(w.dim() == 1 && w.size(0) == P, "clip_step: w must have shape (", P, ",)");
+  TORCH_CHECK(v.device() == x.device() && w.device() == x.device(),
+              "clip_step: v and w must be on x's device");
+  c10::optional<torch::Tensor> out;
+  if (dist) out = torch::zeros({P}, x.options());
+  if (n == 0) return out;
+  const float *xp = x.data_ptr<float>();
+  float *vp = v.data_ptr<float>();
+  TORCH_CHECK((uintptr_t)xp % 16 == 0 && (uintptr_t)vp % 16 == 0,
+              "clip_step: x and v must be 16-byte aligned");
+  const float *wp = w.data_ptr<float>();
+  hipStream_t s = cur_stream();
+#define LAUNCH_CLIP(N, CW) \
+  do { \
+    long nv = n / CW; \
+    int nb = n_blocks(nv, NTHREADS); \
+    if (dist) { \
+      torch::Tensor ws = torch::empty({(long)nb, P}, x.options()); \
+      hipLaunchKernelGGL((k_clip_step<N, CW, true>), dim3(nb), dim3(NTHREADS), 0, s, xp, vp, \
+                         wp, ws.data_ptr<float>(), (int)P, nv, n); \
+      hipLaunchKernelGGL(k_clip_finish, dim3((int)P), dim3(NTHREADS), 0, s, \
+                         ws.data_ptr<float>(), out->data_ptr<float>(), nb, (int)P); \
+    } else { \
+      hipLaunchKernelGGL((k_clip_step<N, CW, false>), dim3(nb), dim3(NTHREADS), 0, s, xp, vp, \
+                         wp, (float *)nullptr, (int)P, nv, n); \
+    } \
+  } while (0)
+  if (P <= 4) LAUNCH_CLIP(4, 4);
+  else if (P <= 8) LAUNCH_CLIP(8, 4);
+  else if (P <= 12) LAUNCH_CLIP(12, 4);
+  else if (P <= 16) LAUNCH_CLIP(16, 4);
+  else if (P <= 24) LAUNCH_CLIP(24, 4);
+  else if (P <= 32) LAUNCH_CLIP(32, 4);
+  else if (P <= 48) LAUNCH_CLIP(48, 2);
+  else LAUNCH_CLIP(64, 2);
+#undef LAUNCH_CLIP
+  return out;
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -1270,4 +1434,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("column_mean_around", &column_mean_around);
   m.def("segment_mean_around", &segment_mean_around);
   m.def("collude", &collude);
+  m.def("clip_step", &clip_step);
 }

@@ -177,6 +177,51 @@ def collude_(x: torch.Tensor, rows, a: float, b: float) -> None:
         x[r] = val
 
 
+@torch.no_grad()
+def clip_step_(x: torch.Tensor, v: torch.Tensor, w: torch.Tensor, dist: bool = True):
+    """One centered-clipping iteration (arXiv:2012.10333) with the clip weights given:
+    in place, v_j += sum over the rows with w_i != 0 of w_i * (x_ij - v_j); returns
+    d2 (P,) with d2_i = sum_j (x_ij - v_j_new)^2 over EVERY row (dist=True), else None.
+
+    x: (P, n) fp32 contiguous, 1 <= P <= 64, n % 4 == 0; v: (n,) fp32; w: (P,) fp32,
+    w_i >= 0, on x's device.  Per column, in fp32: the terms w_i * (x_ij - v_j) are
+    added one at a time in ascending row order, starting from 0, and the sum is then
+    added to v_j.  A row with w_i == 0 is skipped, not multiplied by 0, so a NaN in it
+    cannot reach v; with every w_i == 0, v is not written.  d2 is summed in fp32 in
+    torch's order.  Non-finite values propagate by ordinary IEEE arithmetic.  The HIP
+    kernel does the same in the same row order, up to FMA contraction and the order of
+    the d2 sum: it agrees within the rounding bound, not bit for bit.
+    """
+    if x.dtype != torch.float32 or v.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError(f"clip_step_: x, v and w must be fp32, got {x.dtype}, {v.dtype}, "
+                         f"{w.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"clip_step_: x must be 2D, got {x.dim()}D")
+    if not x.is_contiguous() or not v.is_contiguous():
+        raise ValueError("clip_step_: x and v must be contiguous")
+    P, n = x.shape
+    if not 1 <= P <= 64:
+        raise ValueError(f"clip_step_ supports 1 <= P <= 64, got {P}")
+    if n % 4 != 0:
+        raise ValueError(f"clip_step_: row length must be a multiple of 4, got {n}")
+    if v.shape != (n,):
+        raise ValueError(f"clip_step_: v must have shape ({n},), got {tuple(v.shape)}")
+    if w.shape != (P,):
+        raise ValueError(f"clip_step_: w must have shape ({P},), got {tuple(w.shape)}")
+    if v.device != x.device or w.device != x.device:
+        raise ValueError("clip_step_: v and w must be on x's device")
+    used = [p for p in range(P) if float(w[p]) != 0.0]
+    if used and n > 0:
+        delta = torch.zeros_like(v)
+        for p in used:
+            delta = delta + (x[p] - v) * w[p]
+        v += delta
+    if not dist:
+        return None
+    dev = x - v
+    return (dev * dev).sum(dim=1)
+
+
 # --------------------------------------------------------------------- vote
 @torch.no_grad()
 def rows_equal(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, atol: float) -> torch.Tensor:

@@ -16,6 +16,7 @@ all_gather of the decoded shard.  Reference semantics per policy:
   trimmed_mean (not in the reference) arXiv:1803.01498  (coordinate-wise b-trimmed mean)
   meamed       (not in the reference) arXiv:1802.10116  (mean of the P-b values nearest the median)
   phocas       (not in the reference) arXiv:1805.09682  (mean of the P-b values nearest the b-trimmed mean)
+  centered_clip (not in the reference) arXiv:2012.10333 (iterated clipped steps from the previous aggregate)
   cyclic       cyclic_master.py:103-188             (DFT-code algebraic decode)
 """
 from __future__ import annotations
@@ -146,6 +147,11 @@ class Aggregator:
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
         raise NotImplementedError
+
+    def state(self):
+        """The (d_pad,) flat tensor a checkpoint must carry for this rule to resume
+        exactly, or None: every rule but centered clipping is memoryless."""
+        return None
 
 
 class MeanAggregator(Aggregator):
@@ -659,7 +665,7 @@ class BulyanAggregator(_KrumSelectAggregator):
 
 
 BASELINE_MODES = ("normal/geometric_median/krum/median/trimmed_mean/meamed/phocas/"
-                  "multi_krum/bulyan")
+                  "multi_krum/bulyan/centered_clip")
 
 
 def krum_select_aggregator(mode: str, comm, space, num_workers: int, f: int):
@@ -781,6 +787,90 @@ class MeanAroundAggregator(Aggregator):
         keep, clo, chi = self._bounds(recv.shape[0])
         ops.column_mean_around(recv, keep, clo, chi, self._shard_out)
         self.comm.all_gather_shard(self._shard_out, self._out)
+        return self._out
+
+
+class CenteredClipAggregator(Aggregator):
+    """Centered clipping (Karimireddy, He, Jaggi, "Learning from History for Byzantine
+    Robust Optimization", ICML 2021, arXiv:2012.10333), sharded over d: starting from
+    the PREVIOUS aggregate v, `iters` times
+
+        v <- v + (1/P) sum_i min(1, tau / |x_i - v|) (x_i - v).
+
+    The only stateful rule here: v is the previous output, which after the all_gather is
+    already replicated in self._out, and a rank's v is its own slice of it, so the state
+    costs no buffer and no communication.  It is zero before the first step, and again
+    in the aggregator rebuilt for a survivor world (KNOWN_ISSUES).
+
+    Shape: all_to_all, then iters + 1 passes of ONE kernel over the local shard
+    (ops.clip_step_ applies a clipped step and returns every row's squared distance to
+    the new centre; the first pass has zero weights and only measures) with one
+    allreduce of P floats between them, all_gather.  The P-element clip arithmetic is
+    fp64 torch on device; nothing is read on the host.  last_weights keeps the last
+    iteration's clip factors c_i in [0, 1], on device.
+
+    tau > 0 is the paper's fixed radius.  tau <= 0 or NaN selects AUTO, which is this
+    project's own choice and not the paper's: the lower median (the (P+1)//2-th
+    smallest) of the P distances |x_i - v_0| of the step's first pass, non-finite ones
+    counted as +inf, computed once per step.
+
+    Guarantee and its limits.  A row with a non-finite distance (any NaN/Inf element, or
+    a squared distance that overflows fp32) gets c = 0: it is excluded rather than
+    clipped and, never being read by the update, moves v by nothing.  Every other row
+    moves v by at most tau/P in L2 per iteration.  With at most f < P/2 corrupted rows,
+    auto tau is at most the largest honest distance, so the corrupted rows together
+    move v by at most iters * f/P of it per step.  With a fixed tau the first steps from
+    v = 0 move at most iters * tau per step (the paper's behaviour).  The norm is over
+    the whole gradient (the paper's), not per layer; the pad tail is zero in x and v
+    and stays zero.  The paper pairs the rule with worker-side momentum, which is NOT
+    implemented: without it the variance among honest rows is what time-coupled attacks
+    hide in (profiles/convergence_centered_clip.md).
+    """
+
+    name = "centered_clip"
+    MAX_WORKERS = 64  # the clip-step HIP kernel holds a column in registers, <= 64 rows
+
+    def __init__(self, comm, space, num_workers: int, tau: float = 0.0, iters: int = 3):
+        super().__init__(comm, space)
+        if num_workers > self.MAX_WORKERS:
+            # CPU-side config check: fail at construction, not at the first launch
+            raise ValueError(
+                f"CenteredClipAggregator supports at most {self.MAX_WORKERS} workers "
+                f"(got {num_workers}): the clip-step HIP kernel holds a column in registers")
+        if iters < 1:
+            raise ValueError(f"centered_clip needs iters >= 1, got {iters}")
+        self.num_workers = num_workers
+        tau = float(tau)
+        self.tau = tau if tau > 0.0 else None  # None = auto (tau <= 0 or NaN)
+        self.iters = int(iters)
+        self.last_weights = None
+
+    def state(self) -> torch.Tensor:
+        return self._out
+
+    def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
+        recv = self.exchanged(payload)  # (P, shard)
+        P = recv.shape[0]  # per call: the survivor world has fewer rows
+        if P > self.MAX_WORKERS:
+            raise ValueError(f"centered_clip supports at most {self.MAX_WORKERS} rows, got {P}")
+        shard = self.space.shard
+        v = self._shard_out
+        v.copy_(self._out[self.comm.rank * shard:(self.comm.rank + 1) * shard])
+        inf = float("inf")
+        d2 = ops.clip_step_(recv, v, torch.zeros(P, dtype=torch.float32, device=recv.device))
+        tau = self.tau
+        for it in range(1, self.iters + 1):
+            self.comm.all_reduce(d2)
+            d = d2.double()
+            d = torch.where(torch.isfinite(d), d.sqrt(), torch.full_like(d, inf))
+            if tau is None:
+                tau = torch.kthvalue(d, (P + 1) // 2).values
+            # min(1, tau / d) without the 0/0 and inf/inf of the quotient
+            c = torch.where(d <= tau, torch.ones_like(d), tau / d)
+            c = torch.where(torch.isfinite(d), c, torch.zeros_like(d))
+            d2 = ops.clip_step_(recv, v, (c / P).float(), dist=it < self.iters)
+        self.last_weights = c
+        self.comm.all_gather_shard(v, self._out)
         return self._out
 
 

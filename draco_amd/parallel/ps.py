@@ -30,6 +30,7 @@ from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
 from .aggregators import (
     BASELINE_MODES,
+    CenteredClipAggregator,
     CyclicAggregator,
     GeoMedianAggregator,
     KrumAggregator,
@@ -146,6 +147,9 @@ class Master(_PSBase):
             elif cfg.mode in ("multi_krum", "bulyan"):
                 self.agg = krum_select_aggregator(cfg.mode, local, self.space, self.P,
                                                   cfg.worker_fail)
+            elif cfg.mode == "centered_clip":
+                self.agg = CenteredClipAggregator(local, self.space, num_workers=self.P,
+                                                  tau=cfg.clip_tau, iters=cfg.clip_iters)
             else:
                 raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, "
                                  f"got {cfg.mode!r}")
@@ -168,7 +172,7 @@ class Master(_PSBase):
         if cfg.checkpoint_step > 0:
             load_checkpoint(
                 os.path.join(cfg.train_dir, f"model_step_{cfg.checkpoint_step}"),
-                self.model, self.space, self.opt,
+                self.model, self.space, self.opt, agg=self.agg,
             )
             self.step_num = cfg.checkpoint_step
 
@@ -221,7 +225,7 @@ class Master(_PSBase):
             if cfg.eval_freq > 0 and self.step_num % cfg.eval_freq == 0:
                 save_checkpoint(
                     os.path.join(cfg.train_dir, f"model_step_{self.step_num}"),
-                    self.model, self.space, self.opt, self.step_num, cfg,
+                    self.model, self.space, self.opt, self.step_num, cfg, agg=self.agg,
                 )
         # tell workers to stop (clean shutdown; replaces the reference's missing
         # master-side kill sender, SURVEY §2.3 straggler row)

@@ -39,6 +39,7 @@ from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
 from .aggregators import (
     BASELINE_MODES,
+    CenteredClipAggregator,
     CyclicAggregator,
     GeoMedianAggregator,
     KrumAggregator,
@@ -294,6 +295,9 @@ class Trainer:
             # f = the tolerated adversary count, as Krum takes s = worker_fail
             return krum_select_aggregator(cfg.mode, self.comm, self.space, num_workers,
                                           cfg.worker_fail)
+        if cfg.mode == "centered_clip":
+            return CenteredClipAggregator(self.comm, self.space, num_workers=num_workers,
+                                          tau=cfg.clip_tau, iters=cfg.clip_iters)
         raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, got {cfg.mode!r}")
 
     def _setup_decode(self) -> None:
@@ -810,10 +814,11 @@ class Trainer:
     def save(self):
         self.sync_buffers()  # collective — every rank must call save() together
         if self.rank == 0:
-            save_checkpoint(self._ckpt_path(), self.model, self.space, self.opt, self.step_num, self.cfg)
+            save_checkpoint(self._ckpt_path(), self.model, self.space, self.opt, self.step_num,
+                            self.cfg, agg=self.agg)
 
     def load(self, step: int):
-        load_checkpoint(self._ckpt_path(step), self.model, self.space, self.opt)
+        load_checkpoint(self._ckpt_path(step), self.model, self.space, self.opt, agg=self.agg)
         self.step_num = step
 
     def close(self):

@@ -4,9 +4,10 @@ baseline_master.py:237-248), improved per SURVEY §5.4: state_dict + optimizer s
 resume supported on every rank.
 
 Layout independence: model weights restore through load_state_dict (per-parameter),
-and flat optimizer buffers (momentum / Adam moments) are stored PER PARAMETER via the
-flat-space views — so a checkpoint written under one flat layout (e.g.
-channels_last=False) resumes correctly under another.
+and flat optimizer buffers (momentum / Adam moments) and a stateful aggregation rule's
+state (key "aggregator") are stored PER PARAMETER via the flat-space views — so a
+checkpoint written under one flat layout (e.g. channels_last=False) resumes correctly
+under another.
 """
 from __future__ import annotations
 
@@ -66,8 +67,9 @@ def _strip_compile_prefix(sd: dict) -> dict:
             for k, v in sd.items()}
 
 
-def save_checkpoint(path: str, model, space, opt, step: int, cfg) -> None:
+def save_checkpoint(path: str, model, space, opt, step: int, cfg, agg=None) -> None:
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    agg_state = agg.state() if agg is not None else None
     payload = {
         "step": step,
         "model": {k: v.cpu() for k, v in _strip_compile_prefix(model.state_dict()).items()},
@@ -78,12 +80,16 @@ def save_checkpoint(path: str, model, space, opt, step: int, cfg) -> None:
         # the same synthetic task the checkpoint was trained on
         "synthetic_task": getattr(cfg, "synthetic_task", "means"),
     }
+    if agg_state is not None:
+        # a stateful rule (centered clipping: its previous output), per parameter like
+        # the optimizer buffers; memoryless rules write no key
+        payload["aggregator"] = _flat_to_params(space, agg_state)
     tmp = path + ".tmp"
     torch.save(payload, tmp)
     os.replace(tmp, path)
 
 
-def load_checkpoint(path: str, model, space, opt) -> int:
+def load_checkpoint(path: str, model, space, opt, agg=None) -> int:
     payload = torch.load(path, map_location="cpu", weights_only=False)
     sd = _strip_compile_prefix(payload["model"])  # tolerate old compiled checkpoints
     if any(k.startswith(_COMPILE_PREFIX) for k in model.state_dict()):
@@ -92,4 +98,8 @@ def load_checkpoint(path: str, model, space, opt) -> int:
     model.load_state_dict(sd)
     if opt is not None and payload.get("optimizer") is not None:
         _unpack_opt_state(space, opt, payload["optimizer"])
+    agg_state = agg.state() if agg is not None else None
+    if agg_state is not None and payload.get("aggregator") is not None:
+        # a checkpoint without the key leaves the rule at its initial state
+        _params_to_flat(space, payload["aggregator"], agg_state)
     return payload["step"]

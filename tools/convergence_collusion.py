@@ -1,9 +1,11 @@
 """Every baseline rule against the per-worker rev_grad adversary and the colluding
 ALIE / inner-product adversaries, on CPU through the trainer: LeNet on synthetic MNIST,
 P=7 logical workers in one process, f=1, 40 steps; the cell is the mean of the last five
-training losses.  Prints the markdown table of profiles/convergence_collusion.md.
+training losses.  Prints the markdown table of profiles/convergence_collusion.md and,
+since the centered_clip column (auto radius, 3 iterations) was added, of
+profiles/convergence_centered_clip.md.
 
-  python tools/convergence_collusion.py > profiles/convergence_collusion.md
+  python tools/convergence_collusion.py > profiles/convergence_centered_clip.md
 """
 import argparse
 import os
@@ -20,7 +22,7 @@ from draco_amd.config import Config
 from draco_amd.parallel import Trainer
 
 MODES = ("normal", "median", "trimmed_mean", "meamed", "phocas", "krum", "multi_krum",
-         "bulyan", "geometric_median")
+         "bulyan", "geometric_median", "centered_clip")
 ATTACKS = (("rev_grad", "rev_grad", float("nan")), ("IPM eps=0.1", "ipm", 0.1),
            ("IPM eps=12", "ipm", 12.0), ("ALIE z=1.0", "alie", 1.0), ("ALIE z=1.5", "alie", 1.5))
 
@@ -60,8 +62,9 @@ def main():
               f"{args.batch_size} per worker, {args.steps} steps, fp32.  Each cell is the mean "
               "of the last five training losses (nan: the loss diverged).  A record of one "
               "run, not a test.\n")
-        print(f"Command: `python tools/convergence_collusion.py` on the change that adds the "
-              f"colluding modes (parent commit {commit}).\n")
+        print(f"Command: `python tools/convergence_collusion.py` on the change that adds "
+              f"centered clipping (parent commit {commit}); centered_clip runs with its "
+              "defaults (auto radius, 3 iterations, no worker momentum).\n")
         print(f"First-step loss {clean[0]:.2f}; clean training (normal, no adversary) "
               f"reaches {np.mean(clean[-5:]):.2f}.\n")
         print("| attack | " + " | ".join(MODES) + " |")

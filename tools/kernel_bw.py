@@ -289,6 +289,88 @@ def collude_compare(rounds=3):
         print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def centered_clip_compare(rounds=3, iters=3):
+    """Centered clipping, `iters` iterations on 24 x 11.2M and 8 x 11.2M: the fused route
+    (iters + 1 clip_step_ launches: iters + 1 passes over the block) against the
+    existing-ops route on the same data (per iteration segment_sqdist over one segment +
+    segment_weighted_mean + one add: 2 * iters passes).  Both routes compute the clip
+    factors with the same P-element torch code on device (fixed radius sqrt(d), about
+    the distance of a randn row from 0, so rows are clipped and unclipped), and their
+    results are compared before timing.  Single clip_step_ passes and collude_ (ipm,
+    f=1: the same row passes with one row written) give the per-pass level.  GB/s
+    counts the block passes and the v / out traffic of each route; the arms alternate
+    inside each round; min-max over the rounds per arm."""
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    tau = float(d) ** 0.5
+    seg = torch.tensor([0, d], dtype=torch.int64, device=DEV)
+    for rows in (24, 8):
+        x = torch.randn(rows, d, device=DEV)
+        x[rows // 2:] *= 3.0  # the far half is clipped
+        v = torch.zeros(d, device=DEV)
+        z = torch.zeros(d, device=DEV)
+        zero_w = torch.zeros(rows, device=DEV)
+
+        def factors(d2):
+            dist = d2.double().sqrt()
+            c = torch.where(dist <= tau, torch.ones_like(dist), tau / dist)
+            return torch.where(torch.isfinite(dist), c, torch.zeros_like(dist))
+
+        def fused():
+            v.zero_()
+            d2 = ops.clip_step_(x, v, zero_w)
+            for it in range(1, iters + 1):
+                d2 = ops.clip_step_(x, v, (factors(d2) / rows).float(), dist=it < iters)
+
+        def composed():
+            v.zero_()
+            for it in range(iters):
+                d2 = ops.segment_sqdist(x, v, seg).reshape(rows)
+                w = (factors(d2) / rows).float()
+                ops.segment_weighted_mean(x, w.reshape(rows, 1).contiguous(), seg, z)
+                torch.addcmul(z, v, 1.0 - w.sum(), out=v)  # v = (1 - sum w) v + sum w_i x_i
+
+        fused()
+        got = v.clone()
+        composed()
+        torch.cuda.synchronize()
+        err = float((got - v).abs().max())
+        assert err <= 1e-4 * float(v.abs().max()), (rows, err)
+        print(f"# {rows} rows: max |fused - composed| = {err:.3e}, max |v| = "
+              f"{float(v.abs().max()):.3e}")
+        w_fix = torch.full((rows,), 1.0 / rows, device=DEV)
+        xc = x.clone()  # collude_ writes its row: not into the block the other arms read
+        blk = 4 * rows * d
+        arms = [
+            (f"fused x{iters} ({rows} rows)", fused,
+             (iters + 1) * blk + 4 * d * (1 + 1 + 2 * iters)),
+            (f"composed x{iters} ({rows} rows)", composed,
+             2 * iters * blk + 4 * d * (1 + iters * (1 + 1 + 3))),
+            (f"clip_step_ dist ({rows} rows)", lambda: ops.clip_step_(x, v, w_fix),
+             blk + 8 * d),
+            (f"clip_step_ no dist ({rows} rows)",
+             lambda: ops.clip_step_(x, v, w_fix, dist=False), blk + 8 * d),
+            (f"clip_step_ measure ({rows} rows)", lambda: ops.clip_step_(x, v, zero_w),
+             blk + 4 * d),
+            (f"segment_sqdist ({rows} rows)", lambda: ops.segment_sqdist(x, v, seg),
+             blk + 4 * d),
+            (f"collude_ f=1 ipm ({rows} rows)",
+             lambda: ops.collude_(xc, [rows - 1], -0.1, 0.0), blk),
+        ]
+        times = {name: [] for name, _, _ in arms}
+        for r in range(rounds):
+            print(f"# round {r}")
+            for name, fn, nbytes in arms:
+                ms = t_ms(fn, iters=20, warmup=5)
+                times[name].append(ms)
+                report(name, ms, nbytes)
+        print("# min - max over rounds")
+        for name, _, _ in arms:
+            lo, hi = min(times[name]), max(times[name])
+            print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+        del x, xc, v, z
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -412,6 +494,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("COLLUDE_ONLY") == "1":
         collude_compare()
+        raise SystemExit(0)
+    if os.environ.get("CENTERED_CLIP_ONLY") == "1":
+        centered_clip_compare()
         raise SystemExit(0)
     if os.environ.get("BULYAN_ONLY") == "1":
         bulyan_compare()
