@@ -86,9 +86,35 @@ class Config:
                                   # lower median of the step's distances to the previous
                                   # aggregate; see parallel/aggregators.CenteredClipAggregator)
     clip_iters: int = 3           # mode centered_clip: clipping iterations per step (>= 1)
+    worker_momentum: float = 0.0  # beta of the worker-side momentum (arXiv:2012.10333): every
+                                  # logical worker sends m = beta*m + (1-beta)*g instead of g
+                                  # (0 = off; baseline approach, colocated topology, with
+                                  # --momentum 0 under sgd; see ops.worker_momentum_)
 
     def sanity(self):
         from .coding.collusion import COLLUDING_MODES
+
+        if self.worker_momentum != 0.0:
+            what = f"worker-momentum {self.worker_momentum!r}: "
+            if not 0.0 <= self.worker_momentum < 1.0:  # also catches nan
+                raise ValueError(what + "--worker-momentum must be in [0, 1)")
+            if self.approach != "baseline":
+                raise ValueError(
+                    what + "worker momentum needs --approach baseline (the coded approaches "
+                    "compare or decode the workers' gradients of one step), got "
+                    f"{self.approach!r}")
+            if self.topology == "ps":
+                raise ValueError(
+                    what + "worker momentum needs the colocated topology, not --topology ps")
+            if self.health_timeout > 0:
+                raise ValueError(
+                    what + "worker momentum cannot be combined with --health-timeout (the "
+                    "momentum state of a survivor world is not built)")
+            if self.optimizer == "sgd" and self.momentum != 0.0:
+                raise ValueError(
+                    what + f"worker momentum with --optimizer sgd --momentum {self.momentum!r} "
+                    "would stack two momenta (the server step is x <- x - lr*agg(m)); "
+                    "pass --momentum 0")
 
         if self.err_mode in COLLUDING_MODES:
             what = (f"err-mode {self.err_mode!r} is a colluding mode "

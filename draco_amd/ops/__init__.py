@@ -17,6 +17,7 @@ __all__ = [
     "inject_",
     "collude_",
     "clip_step_",
+    "worker_momentum_",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -119,6 +120,18 @@ def clip_step_(x, v, w, dist=True):
     if ext is not None:
         return ext.clip_step(x, v, w, bool(dist))
     return fallback.clip_step_(x, v, w, dist)
+
+
+def worker_momentum_(g, m, beta, first):
+    """Worker-side momentum, in place on a payload row (or a slice of it) g and the same
+    span of the worker's state m: first -> m = g; else m = beta*m + (1-beta)*g and
+    g = m.  A non-finite g element leaves m as it is and is sent unchanged.  One pass,
+    current stream.  Definition and checks: fallback.worker_momentum_."""
+    ext = _native_for(g)
+    if ext is not None:
+        ext.worker_momentum(g, m, float(beta), bool(first))
+        return
+    fallback.worker_momentum_(g, m, beta, first)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

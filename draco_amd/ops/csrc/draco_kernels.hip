@@ -1407,6 +1407,74 @@ c10::optional<torch::Tensor> clip_step(torch::Tensor x, torch::Tensor v, torch::
   return out;
 }
 
+// --------------------------------------------------------------------------- worker momentum
+// Worker-side momentum ("Learning from History for Byzantine Robust Optimization",
+// arXiv:2012.10333): a logical worker sends m = beta*m + (1-beta)*g instead of g.  One
+// pass over a payload row (or a bucket's slice of it) and the same span of the worker's
+// state row: 8 B read + 8 B written per element, bandwidth-bound like k_sgd.  Per
+// element and branch-free: a non-finite g (NaN, +-Inf) leaves m as it was and is sent
+// as it is, so one overflowing step does not poison the state for the rest of the run.
+// FIRST (the worker's first step): m = g bit for bit (0 where g is non-finite), g is
+// sent unchanged, so m is never read and g never written.  Definition:
+// fallback.worker_momentum_.
+template <bool FIRST>
+__global__ void __launch_bounds__(NTHREADS)
+k_worker_momentum(float4 *__restrict__ g, float4 *__restrict__ m, long n4, float beta,
+                  float omb /* 1-beta, formed in double on the host */) {
+  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  long stride = gridDim.x * (long)blockDim.x;
+  for (; i < n4; i += stride) {
+    float4 gv = g[i];
+    float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+    float mm[4];
+    if (FIRST) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) mm[c] = fabsf(gg[c]) < INFINITY ? gg[c] : 0.f;
+      m[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+    } else {
+      float4 mv = m[i];
+      float old[4] = {mv.x, mv.y, mv.z, mv.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        bool fin = fabsf(gg[c]) < INFINITY;  // false for NaN and +-Inf
+        float upd = fmaf(beta, old[c], omb * gg[c]);
+        mm[c] = fin ? upd : old[c];
+        gg[c] = fin ? upd : gg[c];
+      }
+      m[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+      g[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+    }
+  }
+}
+
+void worker_momentum(torch::Tensor g, torch::Tensor m, double beta, bool first) {
+  CHECK_IN(g);
+  CHECK_IN(m);
+  TORCH_CHECK(g.scalar_type() == torch::kFloat32 && m.scalar_type() == torch::kFloat32,
+              "worker_momentum: g and m must be fp32");
+  TORCH_CHECK(g.device() == m.device(), "worker_momentum: m must be on g's device");
+  TORCH_CHECK(m.numel() == g.numel(), "worker_momentum: m must have g's length, got ",
+              m.numel(), " and ", g.numel());
+  TORCH_CHECK(g.numel() % 4 == 0, "worker_momentum: length must be a multiple of 4");
+  TORCH_CHECK(beta >= 0.0 && beta < 1.0, "worker_momentum: beta must be in [0, 1), got ", beta);
+  if (g.numel() == 0) return;
+  float *gp = g.data_ptr<float>();
+  float *mp = m.data_ptr<float>();
+  TORCH_CHECK((uintptr_t)gp % 16 == 0 && (uintptr_t)mp % 16 == 0,
+              "worker_momentum: g and m must be 16-byte aligned");
+  long n4 = g.numel() / 4;
+  int blocks = n_blocks(n4, NTHREADS);
+  // 1-beta in double, then cast: 1.f - 0.99f is off by 2e-6 relative (see fused_adam_step)
+  float omb = (float)(1.0 - beta);
+  hipStream_t s = cur_stream();
+  if (first)
+    hipLaunchKernelGGL((k_worker_momentum<true>), dim3(blocks), dim3(NTHREADS), 0, s,
+                       (float4 *)gp, (float4 *)mp, n4, (float)beta, omb);
+  else
+    hipLaunchKernelGGL((k_worker_momentum<false>), dim3(blocks), dim3(NTHREADS), 0, s,
+                       (float4 *)gp, (float4 *)mp, n4, (float)beta, omb);
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -1435,4 +1503,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segment_mean_around", &segment_mean_around);
   m.def("collude", &collude);
   m.def("clip_step", &clip_step);
+  m.def("worker_momentum", &worker_momentum);
 }

@@ -222,6 +222,56 @@ def clip_step_(x: torch.Tensor, v: torch.Tensor, w: torch.Tensor, dist: bool = T
     return (dev * dev).sum(dim=1)
 
 
+# --------------------------------------------------------------------- worker momentum
+@torch.no_grad()
+def worker_momentum_(g: torch.Tensor, m: torch.Tensor, beta: float, first: bool) -> None:
+    """Worker-side momentum (arXiv:2012.10333), in place on one worker's gradient g and
+    its private state m: the worker sends its momentum instead of its gradient.
+
+    g, m: 1-D fp32 contiguous, equal length, length % 4 == 0 (a [lo, hi) slice of a
+    payload row and the same slice of the state row qualify); 0 <= beta < 1.  Per
+    element, in fp32:
+      first (the worker's first step):  m = g bit for bit, g is sent as it is.  This is
+          the project's choice, the same as FlatSGD's first step (buf = grad): the
+          paper's m_0 = 0 would scale the first sent row by (1 - beta).
+      later steps:  m = beta*m + (1-beta)*g, then g = m.  (1-beta) is formed in double
+          and then cast, as in fused_adam_step.
+      non-finite g (NaN, +-Inf), any step:  m keeps its value (0 on the first step) and
+          g is sent as it is, so the rule and the nan-guard see the non-finite value in
+          this step and the state stays clean for the next.
+    The HIP kernel contracts the update into one FMA; here it is two products and an
+    add.  They agree within the rounding bound (tests/worker_momentum_util.py), not
+    bit for bit; the first step and the non-finite branches agree bit for bit.
+    """
+    if g.dtype != torch.float32 or m.dtype != torch.float32:
+        raise ValueError(f"worker_momentum_: g and m must be fp32, got {g.dtype}, {m.dtype}")
+    if not g.is_contiguous() or not m.is_contiguous():
+        raise ValueError("worker_momentum_: g and m must be contiguous")
+    if g.device != m.device:
+        raise ValueError("worker_momentum_: m must be on g's device")
+    if m.numel() != g.numel():
+        raise ValueError(f"worker_momentum_: m must have g's length, got {m.numel()} "
+                         f"and {g.numel()}")
+    if g.numel() % 4 != 0:
+        raise ValueError(f"worker_momentum_: length must be a multiple of 4, got {g.numel()}")
+    beta = float(beta)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"worker_momentum_: beta must be in [0, 1), got {beta}")
+    if g.numel() == 0:
+        return
+    g1, m1 = g.view(-1), m.view(-1)
+    fin = torch.isfinite(g1)
+    if first:
+        m1.copy_(torch.where(fin, g1, torch.zeros_like(g1)))
+        return
+    # two rounded products and a rounded add, never an axpy: whether add_(alpha=) fuses
+    # differs between the vector body and the tail of a CPU loop, and a slice of a row
+    # must give the bits the whole row gives (bucketed == whole-row)
+    upd = (m1 * beta).add_(g1 * (1.0 - beta))
+    m1.copy_(torch.where(fin, upd, m1))
+    g1.copy_(torch.where(fin, upd, g1))
+
+
 # --------------------------------------------------------------------- vote
 @torch.no_grad()
 def rows_equal(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, atol: float) -> torch.Tensor:

@@ -822,9 +822,11 @@ class CenteredClipAggregator(Aggregator):
     move v by at most iters * f/P of it per step.  With a fixed tau the first steps from
     v = 0 move at most iters * tau per step (the paper's behaviour).  The norm is over
     the whole gradient (the paper's), not per layer; the pad tail is zero in x and v
-    and stays zero.  The paper pairs the rule with worker-side momentum, which is NOT
-    implemented: without it the variance among honest rows is what time-coupled attacks
-    hide in (profiles/convergence_centered_clip.md).
+    and stays zero.  The paper pairs the rule with worker-side momentum: that is
+    --worker-momentum (Config.worker_momentum, ops.worker_momentum_, applied by the
+    trainer before the rows reach any rule; off by default).  It shrinks the variance
+    among honest rows, which is what time-coupled attacks hide in; what it did in one
+    recorded run is in profiles/convergence_worker_momentum.md.
     """
 
     name = "centered_clip"

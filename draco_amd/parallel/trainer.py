@@ -194,6 +194,17 @@ class Trainer:
             raise ValueError(f"unknown approach {approach!r}")
         self._setup_decode()
 
+        # ---------------- worker-side momentum (arXiv:2012.10333) ----------------
+        # Every local logical worker keeps a private fp32 state row and sends its
+        # momentum instead of its gradient (ops.worker_momentum_); off (no buffer,
+        # no call) at the default beta = 0.  The adversary injection acts on the
+        # sent row only, so every slot keeps an HONEST state: the schedule picks
+        # different Byzantine workers every step.
+        self._wm_beta = float(cfg.worker_momentum)
+        if self._wm_beta > 0.0:
+            self._wm = self.space.alloc_payload(self.L)
+            self._wm_first = [True] * self.L
+
         self.use_graphs = bool(cfg.hip_graphs) and device.type == "cuda" and not cfg.deterministic
         self._graphs = {}
         self._streams = []
@@ -427,6 +438,10 @@ class Trainer:
             return
         lo, hi, _ = self._buckets[bi]
         row = self._hook_row
+        if self._wm_beta > 0.0:
+            # the chunk is final (build_buckets): momentum first, then the injection
+            ops.worker_momentum_(self.payload[row, lo:hi], self._wm[row, lo:hi],
+                                 self._wm_beta, self._wm_first[row])
         if self._hook_adversary:
             # injection at the send boundary, per chunk — same placement as the
             # reference's per-layer err_simulation inside backward (lenet.py:129-141)
@@ -516,6 +531,8 @@ class Trainer:
             if left > 0:
                 self._ship_bucket(bi)
         self.agg.mark_row_started(self._hook_row)
+        if self._wm_beta > 0.0:
+            self._wm_first[self._hook_row] = False  # only now has the whole row shipped
         self._hook_row = None
 
     # ------------------------------------------------------------ hipGraph capture
@@ -662,6 +679,12 @@ class Trainer:
             for l, worker_id, st in pending:
                 if st is not None:  # order the default stream after worker l's graph
                     torch.cuda.current_stream().wait_stream(st)
+                if self._wm_beta > 0.0:
+                    # outside the captured graph: capture runs body() during its
+                    # warm-up, which would advance the state
+                    ops.worker_momentum_(self.payload[l], self._wm[l], self._wm_beta,
+                                         self._wm_first[l])
+                    self._wm_first[l] = False
                 if worker_id in adversaries:
                     self._inject_row(l, 0, self.space.d_pad)
                 # overlap: this row's all_to_all runs while other backwards compute
@@ -811,15 +834,60 @@ class Trainer:
                 b.copy_(flat[off : off + n].view(b.shape).to(b.dtype))
                 off += n
 
+    def _wm_path(self, step: int | None = None) -> str:
+        # rank-local sidecar of the worker-momentum state.  The name must not match
+        # model_step_*, which evaluate.py globs and parses.
+        step = self.step_num if step is None else step
+        return os.path.join(self.cfg.train_dir, f"worker_momentum_step_{step}.rank{self.rank}")
+
     def save(self):
         self.sync_buffers()  # collective — every rank must call save() together
         if self.rank == 0:
             save_checkpoint(self._ckpt_path(), self.model, self.space, self.opt, self.step_num,
                             self.cfg, agg=self.agg)
+        if self._wm_beta > 0.0:
+            # the state is rank-local (P rows over all ranks), so every rank writes its
+            # own rows; per parameter, like the optimizer buffers (layout-independent)
+            from ..utils.checkpoint import _flat_to_params
+
+            path = self._wm_path()
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            state = {
+                "step": self.step_num,
+                "beta": self._wm_beta,
+                "world": self.world,
+                "L": self.L,
+                "first": list(self._wm_first),
+                "rows": [_flat_to_params(self.space, self._wm[l]) for l in range(self.L)],
+            }
+            tmp = path + ".tmp"
+            torch.save(state, tmp)
+            os.replace(tmp, path)
 
     def load(self, step: int):
         load_checkpoint(self._ckpt_path(step), self.model, self.space, self.opt, agg=self.agg)
         self.step_num = step
+        if self._wm_beta > 0.0:
+            self._load_worker_momentum(step)
+
+    def _load_worker_momentum(self, step: int) -> None:
+        from ..utils.checkpoint import _params_to_flat
+
+        path = self._wm_path(step)
+        state = None
+        if os.path.exists(path):
+            state = torch.load(path, map_location="cpu", weights_only=False)
+            if state.get("world") != self.world or state.get("L") != self.L:
+                state = None  # rows of another worker layout are not this rank's workers
+        self._wm.zero_()
+        if state is None:
+            # every slot starts over with m = g on its next step
+            self._wm_first = [True] * self.L
+            self.logger.log({"step": step, "event": "worker_momentum_restart", "path": path})
+            return
+        for l in range(self.L):
+            _params_to_flat(self.space, state["rows"][l], self._wm[l])
+        self._wm_first = [bool(f) for f in state["first"]]
 
     def close(self):
         if self.health is not None:

@@ -6,6 +6,10 @@ since the centered_clip column (auto radius, 3 iterations) was added, of
 profiles/convergence_centered_clip.md.
 
   python tools/convergence_collusion.py > profiles/convergence_centered_clip.md
+
+With --worker-momentum BETA every worker sends its momentum instead of its gradient
+(Config.worker_momentum, with the server's --momentum set to 0 as that flag requires):
+the table of profiles/convergence_worker_momentum.md.
 """
 import argparse
 import os
@@ -32,6 +36,9 @@ def run(args, tmp, mode, err_mode, param, fail):
                  lr=args.lr, dtype="fp32", max_steps=args.steps + 10, eval_freq=0, log_dir="",
                  train_dir=tmp, approach="baseline", mode=mode, worker_fail=fail,
                  err_mode=err_mode, attack_param=param, workers_per_rank=args.workers)
+    if args.worker_momentum != 0.0:
+        cfg.worker_momentum = args.worker_momentum
+        cfg.momentum = 0.0
     t = Trainer(cfg)
     t.logger.stdout_every = 0
     losses = [t.train_step()["loss"] for _ in range(args.steps)]
@@ -46,6 +53,7 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--worker-momentum", type=float, default=0.0)
     args = ap.parse_args()
     torch.set_num_threads(min(torch.get_num_threads(), 8))
     try:
@@ -62,9 +70,17 @@ def main():
               f"{args.batch_size} per worker, {args.steps} steps, fp32.  Each cell is the mean "
               "of the last five training losses (nan: the loss diverged).  A record of one "
               "run, not a test.\n")
-        print(f"Command: `python tools/convergence_collusion.py` on the change that adds "
-              f"centered clipping (parent commit {commit}); centered_clip runs with its "
-              "defaults (auto radius, 3 iterations, no worker momentum).\n")
+        if args.worker_momentum != 0.0:
+            print(f"Command: `python tools/convergence_collusion.py --worker-momentum "
+                  f"{args.worker_momentum} --steps {args.steps}` on the change that adds worker "
+                  f"momentum (parent commit {commit}): every worker sends m = beta*m + "
+                  f"(1-beta)*g with beta = {args.worker_momentum} (m = g on the first step), "
+                  "and the server's SGD momentum is 0 (it is 0.5 without the flag); "
+                  "centered_clip runs with its defaults (auto radius, 3 iterations).\n")
+        else:
+            print(f"Command: `python tools/convergence_collusion.py` on the change that adds "
+                  f"centered clipping (parent commit {commit}); centered_clip runs with its "
+                  "defaults (auto radius, 3 iterations, no worker momentum).\n")
         print(f"First-step loss {clean[0]:.2f}; clean training (normal, no adversary) "
               f"reaches {np.mean(clean[-5:]):.2f}.\n")
         print("| attack | " + " | ".join(MODES) + " |")

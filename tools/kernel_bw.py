@@ -371,6 +371,61 @@ def centered_clip_compare(rounds=3, iters=3):
         del x, xc, v, z
 
 
+def worker_momentum_compare(rounds=3, beta=0.9):
+    """worker_momentum_ (worker-side momentum: m = beta*m + (1-beta)*g, g = m, one launch
+    over one 11.2M-element payload row and its state row, 16 B per element) against the
+    torch route to the same result without the non-finite rule (mul_ + add_, then
+    copy_: three launches, 28 B per element), and against two kernels of the same
+    streaming shape as yardsticks: inject rev_grad (k_axpb, 8 B per element) and
+    fused_sgd with momentum (20 B per element).  The first-step instance reads g and
+    writes m (8 B per element).  Results are compared against the fp64 definition
+    first; the arms alternate inside each round; min-max over the rounds per arm."""
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    omb = 1.0 - beta
+    g0 = torch.randn(d, device=DEV)
+    m0 = torch.randn(d, device=DEV)
+    g0[::1001] = float("nan")
+    g, m = g0.clone(), m0.clone()
+    ops.worker_momentum_(g, m, beta, False)
+    fin = torch.isfinite(g0)
+    exact = beta * m0.double() + omb * g0.double()
+    tol = 4 * 2.0 ** -24 * ((beta * m0.double()).abs() + (omb * g0.double()).abs())
+    assert bool(((m.double() - exact).abs()[fin] <= tol[fin]).all())
+    assert bool((m[~fin] == m0[~fin]).all()) and bool(torch.isnan(g[~fin]).all())
+    assert bool((g[fin] == m[fin]).all())
+    # timed calls feed g = m back in: the values stay finite and settle
+    g, m = torch.randn(d, device=DEV), torch.randn(d, device=DEV)
+    tg, tm = g.clone(), m.clone()
+    p, buf = torch.randn(d, device=DEV), torch.zeros(d, device=DEV)
+    gs = torch.randn(d, device=DEV) * 1e-3
+
+    def torch_route():
+        tm.mul_(beta).add_(tg, alpha=omb)
+        tg.copy_(tm)
+
+    arms = [
+        ("worker_momentum_", lambda: ops.worker_momentum_(g, m, beta, False), 16 * d),
+        ("worker_momentum_ first", lambda: ops.worker_momentum_(g, m, beta, True), 8 * d),
+        ("torch mul_+add_, copy_", torch_route, 28 * d),
+        ("inject rev_grad (8 B/el)", lambda: ops.inject_(gs, "rev_grad"), 8 * d),
+        ("fused_sgd momentum (20 B/el)",
+         lambda: ops.fused_sgd_step(p, gs, buf, lr=0.0, momentum=0.5, dampening=0.0,
+                                    weight_decay=0.0, nesterov=False, first_step=False), 20 * d),
+    ]
+    times = {name: [] for name, _, _ in arms}
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn, nbytes in arms:
+            ms = t_ms(fn, iters=200, warmup=20)
+            times[name].append(ms)
+            report(name, ms, nbytes)
+    print("# min - max over rounds")
+    for name, _, _ in arms:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -497,6 +552,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("CENTERED_CLIP_ONLY") == "1":
         centered_clip_compare()
+        raise SystemExit(0)
+    if os.environ.get("WORKER_MOMENTUM_ONLY") == "1":
+        worker_momentum_compare()
         raise SystemExit(0)
     if os.environ.get("BULYAN_ONLY") == "1":
         bulyan_compare()
