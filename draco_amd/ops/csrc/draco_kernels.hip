@@ -7,23 +7,27 @@
 // the memory ones from the CDNA4 guide: 256-thread blocks (4 waves of 64), float4
 // (16 B/lane) vectorized access, grid-stride loops capped at ~2048 blocks, wave-level
 // __shfl reductions (wave = 64 lanes on CDNA4, not 32).  The exceptions are the three
-// column-sort kernels at the end (k_col_trimmed_mean: median / trimmed mean;
-// k_col_mean_around: mean around median / Phocas; k_seg_mean_around: Multi-Krum /
-// Bulyan over per-segment row selections), which sort each column in registers and are
-// VALU-heavy.  k_collude (colluding ALIE / inner-product adversaries) keeps a column in
-// registers as they do, four columns per lane, without the sort; k_clip_step (centered
-// clipping) does the same and carries per-row distance accumulators on top.
+// column-sort kernels (k_col_trimmed_mean: median / trimmed mean; k_col_mean_around:
+// mean around median / Phocas; k_seg_mean_around: Multi-Krum / Bulyan over per-segment
+// row selections), which sort each column in registers and are VALU-heavy.  k_collude
+// (colluding ALIE / inner-product adversaries) keeps a column in registers as they do,
+// four columns per lane, without the sort; k_clip_step (centered clipping) does the
+// same and carries per-row distance accumulators on top.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
 
 #include <torch/extension.h>
+#include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #define WAVE 64
 #define NTHREADS 256
 
+// --------------------------------------------------------------------------- shared helpers
 static inline int n_blocks(long work, int per_block) {
   long b = (work + per_block - 1) / per_block;
   if (b > 2048) b = 2048;
@@ -40,8 +44,140 @@ static inline int n_blocks(long work, int per_block) {
   CHECK_IN(t); \
   TORCH_CHECK(t.scalar_type() == torch::kInt64, #t " must be int64")
 
-static inline hipStream_t cur_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
+// Every launch of this file: NTHREADS-thread blocks on the current stream, followed by
+// the launch-error check (a hipGetLastError on the host, no synchronisation), so a
+// launch the runtime refuses raises instead of leaving the output as it was.
+template <typename... Params, typename... Args>
+static inline void launch(void (*kernel)(Params...), dim3 grid, size_t lds_bytes,
+                          Args... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(NTHREADS), lds_bytes,
+                     c10::hip::getCurrentHIPStream().stream(), args...);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// The kernels that keep a column of P rows in registers are compiled for the padded
+// sizes below; f gets the smallest one >= P as a std::integral_constant, so that it is
+// a compile-time constant inside a generic lambda.
+template <typename F>
+static inline void for_padded(long P, F &&f) {
+  if (P <= 4) f(std::integral_constant<int, 4>{});
+  else if (P <= 8) f(std::integral_constant<int, 8>{});
+  else if (P <= 12) f(std::integral_constant<int, 12>{});
+  else if (P <= 16) f(std::integral_constant<int, 16>{});
+  else if (P <= 24) f(std::integral_constant<int, 24>{});
+  else if (P <= 32) f(std::integral_constant<int, 32>{});
+  else if (P <= 48) f(std::integral_constant<int, 48>{});
+  else f(std::integral_constant<int, 64>{});
+}
+
+// The optional nan-guard flag of the optimizer steps: an empty tensor means no guard.
+static inline const bool *guard_ptr(const torch::Tensor &guard) {
+  if (guard.numel() == 0) return nullptr;
+  TORCH_CHECK(guard.is_cuda() && guard.scalar_type() == torch::kBool, "guard must be a GPU bool");
+  return guard.data_ptr<bool>();
+}
+
+// x of the vote statistics: (rows, d), with d % 4 == 0 where the kernel reads float4
+static inline void check_rows(const char *op, const torch::Tensor &x, bool vec4) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.dim() == 2, op, ": x must be 2D");
+  TORCH_CHECK(!vec4 || x.size(1) % 4 == 0, op, ": row length must be a multiple of 4");
+}
+
+// ... and the row pairs (a_idx[k], b_idx[k]) of the pairwise ones
+static inline void check_pairs(const char *op, const torch::Tensor &x, const torch::Tensor &a_idx,
+                               const torch::Tensor &b_idx, bool vec4) {
+  check_rows(op, x, vec4);
+  CHECK_IDX(a_idx); CHECK_IDX(b_idx);
+  TORCH_CHECK(a_idx.numel() == b_idx.numel(), op, ": index lengths differ");
+}
+
+// seg holds the L+1 bounds of L segments; returns L
+static inline long segment_count(const char *op, const torch::Tensor &seg) {
+  CHECK_IDX(seg);
+  TORCH_CHECK(seg.dim() == 1 && seg.numel() >= 1, op, ": seg must be 1D with L+1 >= 1 bounds");
+  return seg.numel() - 1;
+}
+
+// The segment kernels stage the bounds in dynamic LDS, and `per_segment` more bytes
+// per segment behind them: L, and the LDS request checked against what a block may take.
+struct SegmentLds { int L; size_t bytes; };
+static inline SegmentLds segment_lds(const char *op, const torch::Tensor &seg,
+                                     size_t per_segment) {
+  long L = segment_count(op, seg);
+  size_t bytes = (size_t)(L + 1) * sizeof(long) + (size_t)L * per_segment;
+  TORCH_CHECK(bytes <= 64 * 1024, op, ": ", L, " segments take ", bytes,
+              " bytes of LDS, a block may take 65536");
+  return {(int)L, bytes};
+}
+
+// Device side of the same: stage the bounds (the caller's __syncthreads() follows) ...
+__device__ __forceinline__ void stage_segments(long *s_seg, const long *__restrict__ seg, int L) {
+  for (int i = threadIdx.x; i <= L; i += blockDim.x) s_seg[i] = seg[i];
+}
+
+// ... whether column i lies in any segment (false for every i when L = 0) ...
+__device__ __forceinline__ bool in_segments(const long *s_seg, int L, long i) {
+  return i >= s_seg[0] && i < s_seg[L];
+}
+
+// ... and, for such a column, the segment l with seg[l] <= i < seg[l+1] (binary search;
+// empty segments are skipped over)
+__device__ __forceinline__ int find_segment(const long *s_seg, int L, long i) {
+  int lo = 0, hi = L - 1;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) >> 1;
+    if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// 64-lane __shfl_down trees: lane 0 ends up with the wave's result
+struct SumOp { __device__ float operator()(float a, float b) const { return a + b; } };
+struct MaxOp { __device__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+
+template <typename Op>
+__device__ __forceinline__ float wave_reduce(float v, Op op) {
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) v = op(v, __shfl_down(v, off, WAVE));
+  return v;
+}
+__device__ __forceinline__ float wave_reduce_sum(float v) { return wave_reduce(v, SumOp{}); }
+__device__ __forceinline__ float wave_reduce_max(float v) { return wave_reduce(v, MaxOp{}); }
+
+// Block step on top: the NTHREADS / WAVE wave results go through LDS and thread 0 folds
+// them onto `init` in ascending wave order.  The return value is the block's result in
+// thread 0 only.
+template <typename Op>
+__device__ __forceinline__ float block_reduce(float wave_result, float init, Op op) {
+  __shared__ float part[NTHREADS / WAVE];
+  if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = wave_result;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int wv = 0; wv < NTHREADS / WAVE; ++wv) init = op(init, part[wv]);
+  return init;
+}
+
+// Column i of the P rows of x into s[0..n): NaN -> +inf (the vote statistics' rule),
+// rows P..n-1 are +inf padding.  n is the caller's compile-time padded size, passed as
+// an argument on purpose: the loop then unrolls only once it is inlined, together with
+// the kernel's own loops, and the kernels compile to what they were with the loop
+// written out in them.  With n a template parameter the loop unrolls before inlining,
+// the loads' loop-invariant address arithmetic is hoisted in another order, and
+// k_col_mean_around measured 0.4-2.5 % slower at P < n
+// (profiles/kernel_bw_shared_helpers.txt).  After unrolling s[] is indexed by
+// compile-time constants only.
+__device__ __forceinline__ void load_column(float *s, int n, const float *x, int P, long stride,
+                                            long i) {
+#pragma unroll
+  for (int p = 0; p < n; ++p) {
+    float v = INFINITY;
+    if (p < P) {
+      v = x[p * stride + i];
+      v = (v != v) ? INFINITY : v;
+    }
+    s[p] = v;
+  }
 }
 
 // --------------------------------------------------------------------------- SGD
@@ -97,26 +233,15 @@ void fused_sgd_step(torch::Tensor param, torch::Tensor grad, torch::Tensor buf,
   auto pp = (float4 *)param.data_ptr<float>();
   auto gg = (const float4 *)grad.data_ptr<float>();
   float4 *bb = nullptr;
-  const bool *gd = nullptr;
-  if (guard.numel() > 0) {
-    TORCH_CHECK(guard.is_cuda() && guard.scalar_type() == torch::kBool, "guard must be a GPU bool");
-    gd = guard.data_ptr<bool>();
-  }
+  const bool *gd = guard_ptr(guard);
   if (mom) {
     CHECK_IN(buf);
     TORCH_CHECK(buf.numel() == param.numel(), "fused_sgd_step: buf must have param's length");
     bb = (float4 *)buf.data_ptr<float>();
   }
-  hipStream_t s = cur_stream();
-  if (mom && nesterov)
-    hipLaunchKernelGGL((k_sgd<true, true>), dim3(blocks), dim3(NTHREADS), 0, s,
-                       pp, gg, bb, n4, (float)lr, (float)momentum, gscale, (float)weight_decay, gd);
-  else if (mom)
-    hipLaunchKernelGGL((k_sgd<true, false>), dim3(blocks), dim3(NTHREADS), 0, s,
-                       pp, gg, bb, n4, (float)lr, (float)momentum, gscale, (float)weight_decay, gd);
-  else
-    hipLaunchKernelGGL((k_sgd<false, false>), dim3(blocks), dim3(NTHREADS), 0, s,
-                       pp, gg, bb, n4, (float)lr, (float)momentum, gscale, (float)weight_decay, gd);
+  auto kernel = mom && nesterov ? k_sgd<true, true> : mom ? k_sgd<true, false> : k_sgd<false, false>;
+  launch(kernel, dim3(blocks), 0, pp, gg, bb, n4, (float)lr, (float)momentum, gscale,
+         (float)weight_decay, gd);
 }
 
 // --------------------------------------------------------------------------- Adam
@@ -178,29 +303,20 @@ void fused_adam_step(torch::Tensor param, torch::Tensor grad, torch::Tensor exp_
   // 1-beta is formed in double: in fp32, 1.f - 0.999f cancels to 1.3e-5 relative
   // error, which lands undiminished in exp_avg_sq (the fallback uses the double too)
   float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-  hipStream_t s = cur_stream();
   auto pp = (float4 *)param.data_ptr<float>();
   auto gg = (const float4 *)grad.data_ptr<float>();
   auto mm = (float4 *)exp_avg.data_ptr<float>();
   auto vv = (float4 *)exp_avg_sq.data_ptr<float>();
-  const bool *gd = nullptr;
-  if (guard.numel() > 0) {
-    TORCH_CHECK(guard.is_cuda() && guard.scalar_type() == torch::kBool, "guard must be a GPU bool");
-    gd = guard.data_ptr<bool>();
-  }
+  float4 *xx = nullptr;
+  const bool *gd = guard_ptr(guard);
   if (amsgrad) {
     CHECK_IN(max_exp_avg_sq);
     TORCH_CHECK(max_exp_avg_sq.numel() == param.numel(),
                 "fused_adam_step: max_exp_avg_sq must have param's length");
-    hipLaunchKernelGGL((k_adam<true>), dim3(blocks), dim3(NTHREADS), 0, s, pp, gg, mm, vv,
-                       (float4 *)max_exp_avg_sq.data_ptr<float>(), n4, lr_t,
-                       (float)beta1, (float)beta2, omb1, omb2, (float)eps,
-                       (float)weight_decay, gd);
-  } else {
-    hipLaunchKernelGGL((k_adam<false>), dim3(blocks), dim3(NTHREADS), 0, s, pp, gg, mm, vv,
-                       nullptr, n4, lr_t, (float)beta1, (float)beta2, omb1, omb2,
-                       (float)eps, (float)weight_decay, gd);
+    xx = (float4 *)max_exp_avg_sq.data_ptr<float>();
   }
+  launch(amsgrad ? k_adam<true> : k_adam<false>, dim3(blocks), 0, pp, gg, mm, vv, xx, n4, lr_t,
+         (float)beta1, (float)beta2, omb1, omb2, (float)eps, (float)weight_decay, gd);
 }
 
 // --------------------------------------------------------------------------- inject
@@ -225,8 +341,7 @@ void inject(torch::Tensor grad, std::string mode, bool cyclic) {
   else TORCH_CHECK(false, "inject: unknown mode ", mode);
   TORCH_CHECK(grad.numel() % 4 == 0, "inject: length must be a multiple of 4");
   long n4 = grad.numel() / 4;
-  hipLaunchKernelGGL(k_axpb, dim3(n_blocks(n4, NTHREADS)), dim3(NTHREADS), 0, cur_stream(),
-                     (float4 *)grad.data_ptr<float>(), n4, a, b);
+  launch(k_axpb, dim3(n_blocks(n4, NTHREADS)), 0, (float4 *)grad.data_ptr<float>(), n4, a, b);
 }
 
 // --------------------------------------------------------------------------- vote
@@ -253,19 +368,14 @@ __global__ void k_rows_equal(const float4 *__restrict__ x, const long *__restric
 
 torch::Tensor rows_equal(torch::Tensor x, torch::Tensor a_idx, torch::Tensor b_idx,
                          double atol) {
-  CHECK_IN(x); CHECK_IDX(a_idx); CHECK_IDX(b_idx);
-  TORCH_CHECK(x.dim() == 2, "rows_equal: x must be 2D");
-  TORCH_CHECK(a_idx.numel() == b_idx.numel(), "rows_equal: index lengths differ");
+  check_pairs("rows_equal", x, a_idx, b_idx, true);
   long k = a_idx.numel();
   long d = x.size(1);
-  TORCH_CHECK(d % 4 == 0, "rows_equal: row length must be a multiple of 4");
   auto out = torch::ones({k}, torch::dtype(torch::kUInt8).device(x.device()));
   if (d == 0 || k == 0) return out;
   dim3 grid(n_blocks(d / 4, NTHREADS), (unsigned)k);
-  hipLaunchKernelGGL(k_rows_equal, grid, dim3(NTHREADS), 0, cur_stream(),
-                     (const float4 *)x.data_ptr<float>(), a_idx.data_ptr<long>(),
-                     b_idx.data_ptr<long>(), out.data_ptr<unsigned char>(), d / 4, d / 4,
-                     (float)atol);
+  launch(k_rows_equal, grid, 0, (const float4 *)x.data_ptr<float>(), a_idx.data_ptr<long>(),
+         b_idx.data_ptr<long>(), out.data_ptr<unsigned char>(), d / 4, d / 4, (float)atol);
   return out;
 }
 
@@ -311,58 +421,43 @@ __global__ void k_absmax(const float4 *__restrict__ x, const long *__restrict__ 
                      max(__float_as_int(a.z) & 0x7fffffff, __float_as_int(a.w) & 0x7fffffff)));
   }
   float mx = __int_as_float(min(mi, 0x7f800000));
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off, WAVE));
-  __shared__ float wmax[NTHREADS / WAVE];
-  int wid = threadIdx.x / WAVE;
-  if ((threadIdx.x & (WAVE - 1)) == 0) wmax[wid] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = wmax[0];
-    for (int wv = 1; wv < NTHREADS / WAVE; ++wv) tot = fmaxf(tot, wmax[wv]);
-    atomic_max_f32(&out[row], tot);
-  }
+  // mx >= +0 and never NaN, so folding onto 0 changes nothing
+  float tot = block_reduce(wave_reduce_max(mx), 0.f, MaxOp{});
+  if (threadIdx.x == 0) atomic_max_f32(&out[row], tot);
 }
 
 torch::Tensor pair_maxdiff(torch::Tensor x, torch::Tensor a_idx, torch::Tensor b_idx) {
-  CHECK_IN(x); CHECK_IDX(a_idx); CHECK_IDX(b_idx);
-  TORCH_CHECK(x.dim() == 2, "pair_maxdiff: x must be 2D");
-  TORCH_CHECK(a_idx.numel() == b_idx.numel(), "pair_maxdiff: index lengths differ");
+  check_pairs("pair_maxdiff", x, a_idx, b_idx, true);
   long k = a_idx.numel(), d = x.size(1);
-  TORCH_CHECK(d % 4 == 0, "pair_maxdiff: row length must be a multiple of 4");
   auto out = torch::zeros({k}, torch::dtype(torch::kFloat32).device(x.device()));
   if (d == 0 || k == 0) return out;
   dim3 grid(n_blocks(d / 4 / 8, NTHREADS), (unsigned)k);
-  hipLaunchKernelGGL((k_absmax<true>), grid, dim3(NTHREADS), 0, cur_stream(),
-                     (const float4 *)x.data_ptr<float>(), a_idx.data_ptr<long>(),
-                     b_idx.data_ptr<long>(), out.data_ptr<float>(), d / 4, d / 4);
+  launch(k_absmax<true>, grid, 0, (const float4 *)x.data_ptr<float>(), a_idx.data_ptr<long>(),
+         b_idx.data_ptr<long>(), out.data_ptr<float>(), d / 4, d / 4);
   return out;
 }
 
 torch::Tensor row_absmax(torch::Tensor x) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dim() == 2, "row_absmax: x must be 2D");
+  check_rows("row_absmax", x, true);
   long m = x.size(0), d = x.size(1);
-  TORCH_CHECK(d % 4 == 0, "row_absmax: row length must be a multiple of 4");
   auto out = torch::zeros({m}, torch::dtype(torch::kFloat32).device(x.device()));
   if (d == 0 || m == 0) return out;
   dim3 grid(n_blocks(d / 4 / 8, NTHREADS), (unsigned)m);
-  hipLaunchKernelGGL((k_absmax<false>), grid, dim3(NTHREADS), 0, cur_stream(),
-                     (const float4 *)x.data_ptr<float>(), nullptr, nullptr,
-                     out.data_ptr<float>(), d / 4, d / 4);
+  launch(k_absmax<false>, grid, 0, (const float4 *)x.data_ptr<float>(), nullptr, nullptr,
+         out.data_ptr<float>(), d / 4, d / 4);
   return out;
 }
 
 // Per-SEGMENT tolerance-vote statistics: the segment-granular vote bounds a
 // within-tolerance adversary to rtol*segmax per parameter tensor instead of
 // rtol*rowmax over the whole gradient (~10x tighter for late small layers).
-// Same layout as k_seg_sqdist: segment bounds in LDS, binary search per element,
-// flush-on-segment-change with a float atomic max.
-// The grid-stride loop makes a thread's CONSECUTIVE elements gstride apart, i.e.
-// almost always in DIFFERENT segments — so flush-on-segment-change degenerates to
-// one GLOBAL atomic per element (measured 4-7 GB/s).  Instead each block
-// accumulates into an LDS per-segment array (LDS atomics: conflict-serialised but
-// ~3 orders cheaper than L2) and flushes ONCE per (block, segment).
+// Same layout as k_seg_sqdist: segment bounds in LDS (stage_segments), find_segment
+// per element.  The grid-stride loop makes a thread's CONSECUTIVE elements gstride
+// apart, i.e. almost always in DIFFERENT segments — so a per-thread running maximum
+// flushed on segment change degenerates to one GLOBAL atomic per element (measured
+// 4-7 GB/s).  Instead each block accumulates into an LDS per-segment array (LDS
+// atomics: conflict-serialised but ~3 orders cheaper than L2) and flushes ONCE per
+// (block, segment).
 template <bool PAIR>
 __global__ void k_seg_absmax(const float *__restrict__ x, const long *__restrict__ ai,
                              const long *__restrict__ bi, const long *__restrict__ seg,
@@ -371,7 +466,7 @@ __global__ void k_seg_absmax(const float *__restrict__ x, const long *__restrict
   extern __shared__ char smem[];
   long *s_seg = (long *)smem;
   int *s_max = (int *)(smem + (L + 1) * sizeof(long));  // float bits (non-negative)
-  for (int i = threadIdx.x; i <= L; i += blockDim.x) s_seg[i] = seg[i];
+  stage_segments(s_seg, seg, L);
   for (int i = threadIdx.x; i < L; i += blockDim.x) s_max[i] = 0;
   __syncthreads();
   int r = blockIdx.y;
@@ -383,21 +478,16 @@ __global__ void k_seg_absmax(const float *__restrict__ x, const long *__restrict
   // common case — pre-reduces in registers and issues ONE LDS atomic)
   for (long base = blockIdx.x * (long)blockDim.x; base < d; base += gstride) {
     long i = base + threadIdx.x;
-    bool valid = (i < d) && i >= s_seg[0] && i < s_seg[L];
+    bool valid = (i < d) && in_segments(s_seg, L, i);
     int lo = 0;
     float v = 0.f;
     if (valid) {
-      int hi = L - 1;
-      while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
-      }
+      lo = find_segment(s_seg, L, i);
       v = abs_nan_inf(PAIR ? (ra[i] - rb[i]) : ra[i]);  // feeds both paths below
     }
     int lo0 = __shfl(lo, 0, WAVE);
     if (__all(valid && lo == lo0)) {
-#pragma unroll
-      for (int off = WAVE / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, WAVE));
+      v = wave_reduce_max(v);
       if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(&s_max[lo0], __float_as_int(v));
     } else if (valid) {
       atomicMax(&s_max[lo], __float_as_int(v));
@@ -411,34 +501,27 @@ __global__ void k_seg_absmax(const float *__restrict__ x, const long *__restrict
 }
 
 torch::Tensor segment_absmax(torch::Tensor x, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IDX(seg);
+  check_rows("segment_absmax", x, false);
+  SegmentLds sl = segment_lds("segment_absmax", seg, sizeof(int));
   long m = x.size(0), d = x.size(1);
-  int L = (int)seg.numel() - 1;
-  auto out = torch::zeros({m, L}, torch::dtype(torch::kFloat32).device(x.device()));
+  auto out = torch::zeros({m, sl.L}, torch::dtype(torch::kFloat32).device(x.device()));
   if (d == 0 || m == 0) return out;
   dim3 grid(n_blocks(d / 8, NTHREADS), (unsigned)m);
-  size_t smem = (L + 1) * sizeof(long) + L * sizeof(int);
-  hipLaunchKernelGGL((k_seg_absmax<false>), grid, dim3(NTHREADS), smem,
-                     cur_stream(), x.data_ptr<float>(), nullptr, nullptr,
-                     seg.data_ptr<long>(), L, out.data_ptr<float>(), d, d);
+  launch(k_seg_absmax<false>, grid, sl.bytes, x.data_ptr<float>(), nullptr, nullptr,
+         seg.data_ptr<long>(), sl.L, out.data_ptr<float>(), d, d);
   return out;
 }
 
 torch::Tensor segment_pair_maxdiff(torch::Tensor x, torch::Tensor a_idx,
                                    torch::Tensor b_idx, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IDX(a_idx); CHECK_IDX(b_idx); CHECK_IDX(seg);
-  TORCH_CHECK(x.dim() == 2, "segment_pair_maxdiff: x must be 2D");
-  TORCH_CHECK(a_idx.numel() == b_idx.numel(), "segment_pair_maxdiff: index lengths differ");
+  check_pairs("segment_pair_maxdiff", x, a_idx, b_idx, false);
+  SegmentLds sl = segment_lds("segment_pair_maxdiff", seg, sizeof(int));
   long k = a_idx.numel(), d = x.size(1);
-  int L = (int)seg.numel() - 1;
-  auto out = torch::zeros({k, L}, torch::dtype(torch::kFloat32).device(x.device()));
+  auto out = torch::zeros({k, sl.L}, torch::dtype(torch::kFloat32).device(x.device()));
   if (d == 0 || k == 0) return out;
   dim3 grid(n_blocks(d / 8, NTHREADS), (unsigned)k);
-  size_t smem = (L + 1) * sizeof(long) + L * sizeof(int);
-  hipLaunchKernelGGL((k_seg_absmax<true>), grid, dim3(NTHREADS), smem,
-                     cur_stream(), x.data_ptr<float>(), a_idx.data_ptr<long>(),
-                     b_idx.data_ptr<long>(), seg.data_ptr<long>(), L,
-                     out.data_ptr<float>(), d, d);
+  launch(k_seg_absmax<true>, grid, sl.bytes, x.data_ptr<float>(), a_idx.data_ptr<long>(),
+         b_idx.data_ptr<long>(), seg.data_ptr<long>(), sl.L, out.data_ptr<float>(), d, d);
   return out;
 }
 
@@ -473,10 +556,10 @@ static void launch_combine(torch::Tensor x, torch::Tensor rows, torch::Tensor w,
               "combine: 16-byte alignment required");
   TORCH_CHECK(w.numel() == rows.numel(), "combine: one weight per row index required");
   TORCH_CHECK(x.dim() == 2 && d <= x.size(1), "combine: out is longer than a row of x");
-  hipLaunchKernelGGL(k_combine, dim3(n_blocks(d / 4, NTHREADS)), dim3(NTHREADS), 0,
-                     cur_stream(), (const float4 *)(x.data_ptr<float>() + col_off),
-                     rows.data_ptr<long>(), w.data_ptr<float>(), (int)rows.numel(),
-                     (float4 *)out.data_ptr<float>(), d / 4, stride_elems / 4);
+  launch(k_combine, dim3(n_blocks(d / 4, NTHREADS)), 0,
+         (const float4 *)(x.data_ptr<float>() + col_off), rows.data_ptr<long>(),
+         w.data_ptr<float>(), (int)rows.numel(), (float4 *)out.data_ptr<float>(), d / 4,
+         stride_elems / 4);
 }
 
 // Bucketed cyclic encode (per-layer overlap): combine only the [col_off,
@@ -538,11 +621,10 @@ void cyclic_encode(torch::Tensor grads, torch::Tensor w_re, torch::Tensor w_im,
   TORCH_CHECK(stride >= d, "cyclic_encode: grads rows are shorter than out rows");
   TORCH_CHECK(w_re.numel() == grads.size(0) && w_im.numel() == grads.size(0),
               "cyclic_encode: w_re and w_im need one weight per grads row");
-  hipLaunchKernelGGL(k_encode2, dim3(n_blocks(d / 4, NTHREADS)), dim3(NTHREADS), 0,
-                     cur_stream(), (const float4 *)grads.data_ptr<float>(),
-                     w_re.data_ptr<float>(), w_im.data_ptr<float>(), (int)grads.size(0),
-                     (float4 *)out.data_ptr<float>(),
-                     (float4 *)out.data_ptr<float>() + d / 4, d / 4, stride / 4);
+  launch(k_encode2, dim3(n_blocks(d / 4, NTHREADS)), 0,
+         (const float4 *)grads.data_ptr<float>(), w_re.data_ptr<float>(),
+         w_im.data_ptr<float>(), (int)grads.size(0), (float4 *)out.data_ptr<float>(),
+         (float4 *)out.data_ptr<float>() + d / 4, d / 4, stride / 4);
 }
 
 void cyclic_recombine(torch::Tensor r_planes, torch::Tensor v_re, torch::Tensor v_im,
@@ -562,8 +644,8 @@ void cyclic_recombine(torch::Tensor r_planes, torch::Tensor v_re, torch::Tensor 
 
 // --------------------------------------------------------------------------- project
 // K3 (cyclic_master.py:154): partial projection proj[i] = sum_d R[i,d] * z[d] over the
-// local shard.  One block row per (worker, plane); wave shuffle reduce (64-lane) then
-// LDS across the block's 4 waves, one atomicAdd per block.
+// local shard.  One block row per (worker, plane); wave_reduce_sum, then block_reduce
+// across the block's 4 waves, one atomicAdd per block.
 __global__ void k_project(const float4 *__restrict__ r, const float4 *__restrict__ z,
                           float *__restrict__ out, long d4, long stride4) {
   int row = blockIdx.y;
@@ -578,17 +660,8 @@ __global__ void k_project(const float4 *__restrict__ r, const float4 *__restrict
     acc = fmaf(a.z, b.z, acc);
     acc = fmaf(a.w, b.w, acc);
   }
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, WAVE);
-  __shared__ float warp_acc[NTHREADS / WAVE];
-  int wid = threadIdx.x / WAVE;
-  if ((threadIdx.x & (WAVE - 1)) == 0) warp_acc[wid] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int wv = 0; wv < NTHREADS / WAVE; ++wv) tot += warp_acc[wv];
-    atomicAdd(&out[row], tot);
-  }
+  float tot = block_reduce(wave_reduce_sum(acc), 0.f, SumOp{});
+  if (threadIdx.x == 0) atomicAdd(&out[row], tot);
 }
 
 torch::Tensor cyclic_project(torch::Tensor rows, torch::Tensor z) {
@@ -599,12 +672,10 @@ torch::Tensor cyclic_project(torch::Tensor rows, torch::Tensor z) {
   TORCH_CHECK(d % 4 == 0, "cyclic_project: row length must be a multiple of 4");
   TORCH_CHECK(z.numel() == d, "cyclic_project: z must have the rows' length");
   auto out = torch::zeros({m}, torch::dtype(torch::kFloat32).device(rows.device()));
-  if (d == 0) return out;
+  if (d == 0 || m == 0) return out;
   dim3 grid(n_blocks(d / 4 / 8, NTHREADS), (unsigned)m);
-  hipLaunchKernelGGL(k_project, grid, dim3(NTHREADS), 0, cur_stream(),
-                     (const float4 *)rows.data_ptr<float>(),
-                     (const float4 *)z.data_ptr<float>(), out.data_ptr<float>(), d / 4,
-                     d / 4);
+  launch(k_project, grid, 0, (const float4 *)rows.data_ptr<float>(),
+         (const float4 *)z.data_ptr<float>(), out.data_ptr<float>(), d / 4, d / 4);
   return out;
 }
 
@@ -615,19 +686,18 @@ void combine_rows(torch::Tensor x, torch::Tensor rows, torch::Tensor w, torch::T
 
 // --------------------------------------------------------------------------- geomed
 // K6 (baseline_master.py:271-276 / hdmedians): per-(worker, layer-segment) partial
-// squared distances for the sharded Weiszfeld iteration.  Segment bounds live in LDS;
-// each thread keeps a running (segment, acc) and flushes on change via atomicAdd.
-// Same LDS-accumulate pattern as k_seg_absmax (see comment there): grid-stride
-// means per-element segment changes, so per-thread flush-on-change would cost one
-// GLOBAL atomic per element.  Blocks accumulate per-segment partial sums in LDS
-// and flush once per (block, segment).
+// squared distances for the sharded Weiszfeld iteration.  Segment bounds live in LDS
+// (stage_segments), find_segment per element.  Same LDS-accumulate pattern as
+// k_seg_absmax (see comment there): grid-stride means per-element segment changes, so
+// per-thread flush-on-change would cost one GLOBAL atomic per element.  Blocks
+// accumulate per-segment partial sums in LDS and flush once per (block, segment).
 __global__ void k_seg_sqdist(const float *__restrict__ x, const float *__restrict__ z,
                              const long *__restrict__ seg, int L,
                              float *__restrict__ out /* (P, L) */, long d, long stride) {
   extern __shared__ char smem[];
   long *s_seg = (long *)smem;
   float *s_acc = (float *)(smem + (L + 1) * sizeof(long));
-  for (int i = threadIdx.x; i <= L; i += blockDim.x) s_seg[i] = seg[i];
+  stage_segments(s_seg, seg, L);
   for (int i = threadIdx.x; i < L; i += blockDim.x) s_acc[i] = 0.f;
   __syncthreads();
   int p = blockIdx.y;
@@ -635,23 +705,17 @@ __global__ void k_seg_sqdist(const float *__restrict__ x, const float *__restric
   long gstride = gridDim.x * (long)blockDim.x;
   for (long base = blockIdx.x * (long)blockDim.x; base < d; base += gstride) {
     long i = base + threadIdx.x;
-    bool valid = (i < d) && i >= s_seg[0] && i < s_seg[L];
+    bool valid = (i < d) && in_segments(s_seg, L, i);
     int lo = 0;
     float c = 0.f;
     if (valid) {
-      // binary search: segment l with seg[l] <= i < seg[l+1]
-      int hi = L - 1;
-      while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
-      }
+      lo = find_segment(s_seg, L, i);
       float dlt = row[i] - z[i];
       c = dlt * dlt;
     }
     int lo0 = __shfl(lo, 0, WAVE);
     if (__all(valid && lo == lo0)) {  // whole wave in one segment: one LDS atomic
-#pragma unroll
-      for (int off = WAVE / 2; off > 0; off >>= 1) c += __shfl_down(c, off, WAVE);
+      c = wave_reduce_sum(c);
       if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&s_acc[lo0], c);
     } else if (valid) {
       atomicAdd(&s_acc[lo], c);
@@ -663,18 +727,16 @@ __global__ void k_seg_sqdist(const float *__restrict__ x, const float *__restric
 }
 
 torch::Tensor segment_sqdist(torch::Tensor x, torch::Tensor z, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IN(z); CHECK_IDX(seg);
+  CHECK_IN(x); CHECK_IN(z);
   TORCH_CHECK(x.dim() == 2 && z.numel() == x.size(1),
               "segment_sqdist: z must have the length of a row of x");
+  SegmentLds sl = segment_lds("segment_sqdist", seg, sizeof(float));
   long P = x.size(0), d = x.size(1);
-  int L = (int)seg.numel() - 1;
-  auto out = torch::zeros({P, L}, torch::dtype(torch::kFloat32).device(x.device()));
-  if (d == 0) return out;
+  auto out = torch::zeros({P, sl.L}, torch::dtype(torch::kFloat32).device(x.device()));
+  if (d == 0 || P == 0) return out;
   dim3 grid(n_blocks(d / 4, NTHREADS), (unsigned)P);
-  size_t smem = (L + 1) * sizeof(long) + L * sizeof(float);
-  hipLaunchKernelGGL(k_seg_sqdist, grid, dim3(NTHREADS), smem,
-                     cur_stream(), x.data_ptr<float>(), z.data_ptr<float>(),
-                     seg.data_ptr<long>(), L, out.data_ptr<float>(), d, d);
+  launch(k_seg_sqdist, grid, sl.bytes, x.data_ptr<float>(), z.data_ptr<float>(),
+         seg.data_ptr<long>(), sl.L, out.data_ptr<float>(), d, d);
   return out;
 }
 
@@ -683,19 +745,15 @@ __global__ void k_seg_wmean(const float *__restrict__ x, const float *__restrict
                             const long *__restrict__ seg, int L, int P,
                             float *__restrict__ out, long d, long stride) {
   extern __shared__ long s_seg[];
-  for (int i = threadIdx.x; i <= L; i += blockDim.x) s_seg[i] = seg[i];
+  stage_segments(s_seg, seg, L);
   __syncthreads();
   long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
   long gstride = gridDim.x * (long)blockDim.x;
   for (; i < d; i += gstride) {
-    if (i < s_seg[0] || i >= s_seg[L]) continue;  // outside all segments: out is
+    if (!in_segments(s_seg, L, i)) continue;  // outside all segments: out is
     // left untouched, matching the CPU fallback (callers zero-init the buffer;
     // the [d, d_pad) padding tail must stay zero)
-    int lo = 0, hi = L - 1;
-    while (lo < hi) {
-      int mid = (lo + hi + 1) >> 1;
-      if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
-    }
+    int lo = find_segment(s_seg, L, i);
     float acc = 0.f;
     for (int p = 0; p < P; ++p) acc = fmaf(w[p * L + lo], x[p * stride + i], acc);
     out[i] = acc;
@@ -704,17 +762,15 @@ __global__ void k_seg_wmean(const float *__restrict__ x, const float *__restrict
 
 void segment_weighted_mean(torch::Tensor x, torch::Tensor w, torch::Tensor seg,
                            torch::Tensor out) {
-  CHECK_IN(x); CHECK_IN(w); CHECK_IDX(seg); CHECK_IN(out);
+  CHECK_IN(x); CHECK_IN(w); CHECK_IN(out);
   TORCH_CHECK(x.dim() == 2, "segment_weighted_mean: x must be 2D");
+  SegmentLds sl = segment_lds("segment_weighted_mean", seg, 0);
   long P = x.size(0), d = x.size(1);
-  int L = (int)seg.numel() - 1;
-  TORCH_CHECK(w.numel() == P * L, "segment_weighted_mean: w must be (P, L)");
+  TORCH_CHECK(w.numel() == P * sl.L, "segment_weighted_mean: w must be (P, L)");
   TORCH_CHECK(out.numel() >= d, "segment_weighted_mean: out is shorter than a row of x");
   if (d == 0) return;
-  hipLaunchKernelGGL(k_seg_wmean, dim3(n_blocks(d, NTHREADS)), dim3(NTHREADS),
-                     (L + 1) * sizeof(long), cur_stream(), x.data_ptr<float>(),
-                     w.data_ptr<float>(), seg.data_ptr<long>(), L, (int)P,
-                     out.data_ptr<float>(), d, d);
+  launch(k_seg_wmean, dim3(n_blocks(d, NTHREADS)), sl.bytes, x.data_ptr<float>(),
+         w.data_ptr<float>(), seg.data_ptr<long>(), sl.L, (int)P, out.data_ptr<float>(), d, d);
 }
 
 // --------------------------------------------------------------------------- krum
@@ -763,9 +819,9 @@ __global__ void k_seg_gram(const float *__restrict__ x, const long *__restrict__
 }
 
 torch::Tensor segment_gram(torch::Tensor x, torch::Tensor seg) {
-  CHECK_IN(x); CHECK_IDX(seg);
+  check_rows("segment_gram", x, false);
+  long L = segment_count("segment_gram", seg);
   long P = x.size(0), d = x.size(1);
-  int L = (int)seg.numel() - 1;
   TORCH_CHECK(P <= 32, "segment_gram kernel supports P <= 32");
   auto out = torch::zeros({L, P, P}, torch::dtype(torch::kFloat32).device(x.device()));
   // host-side chunk descriptors
@@ -782,9 +838,8 @@ torch::Tensor segment_gram(torch::Tensor x, torch::Tensor seg) {
   if (desc.empty()) return out;
   auto desc_t = torch::from_blob(desc.data(), {(long)desc.size()}, torch::kInt64)
                     .clone().to(x.device());
-  hipLaunchKernelGGL(k_seg_gram, dim3((unsigned)(desc.size() / 3)), dim3(NTHREADS), 0,
-                     cur_stream(), x.data_ptr<float>(), desc_t.data_ptr<long>(), (int)P,
-                     out.data_ptr<float>(), d);
+  launch(k_seg_gram, dim3((unsigned)(desc.size() / 3)), 0, x.data_ptr<float>(),
+         desc_t.data_ptr<long>(), (int)P, out.data_ptr<float>(), d);
   return out;
 }
 
@@ -794,12 +849,13 @@ torch::Tensor segment_gram(torch::Tensor x, torch::Tensor seg) {
 // and average ranks [lo, hi) — added one at a time in ascending order, so the result
 // is bit-identical to the CPU fallback.  Median: lo=(P-1)/2, hi=P/2+1.
 //
-// The only kernel in this file that sorts.  Each lane owns whole columns (consecutive
-// lanes on consecutive columns: every row read is one coalesced 256 B wave access)
-// and sorts in REGISTERS: the array s[] is only ever indexed by compile-time
-// constants (a fully unrolled sorting network over the padded size N), because a
-// runtime-indexed per-thread array goes to scratch.  Rows P..N-1 are +inf: they sort
-// to the top and never enter [lo, hi) since hi <= P.  fminf/fmaxf never see a NaN, so
+// The first of the three kernels that sort (k_col_mean_around and k_seg_mean_around
+// share its sort).  Each lane owns whole columns (consecutive lanes on consecutive
+// columns: every row read is one coalesced 256 B wave access) and sorts in REGISTERS:
+// the array s[] is only ever indexed by compile-time constants (a fully unrolled
+// sorting network over the padded size N, chosen by for_padded), because a
+// runtime-indexed per-thread array goes to scratch.  load_column's +inf padding rows
+// sort to the top and never enter [lo, hi) since hi <= P.  fminf/fmaxf never see a NaN, so
 // each compare-exchange is an exact permutation of its two inputs.
 //
 // The network is Batcher's merge exchange (Knuth 5.2.2 Algorithm M), built at compile
@@ -851,15 +907,7 @@ k_col_trimmed_mean(const float *__restrict__ x, int P, int lo, int hi, float cnt
   long gstride = gridDim.x * (long)blockDim.x;
   for (; i < d; i += gstride) {
     float s[N];
-#pragma unroll
-    for (int p = 0; p < N; ++p) {
-      float v = INFINITY;
-      if (p < P) {
-        v = x[p * stride + i];
-        v = (v != v) ? INFINITY : v;
-      }
-      s[p] = v;
-    }
+    load_column(s, N, x, P, stride, i);
     sort_columns(s, std::make_integer_sequence<int, kMergeExchange<N>.n>{});
     // -0.0f + v == v bit for bit (v = -0.0f included), so the first kept rank needs
     // no case of its own
@@ -884,22 +932,13 @@ void column_trimmed_mean(torch::Tensor x, long lo, long hi, torch::Tensor out) {
   TORCH_CHECK(d % 4 == 0, "column_trimmed_mean: row length must be a multiple of 4");
   if (d == 0) return;
   dim3 grid(n_blocks(d, NTHREADS));
-  hipStream_t s = cur_stream();
   const float *xp = x.data_ptr<float>();
   float *op = out.data_ptr<float>();
   float cnt = (float)(hi - lo);
-#define LAUNCH_CTM(N) \
-  hipLaunchKernelGGL((k_col_trimmed_mean<N>), grid, dim3(NTHREADS), 0, s, xp, (int)P, \
-                     (int)lo, (int)hi, cnt, op, d, d)
-  if (P <= 4) LAUNCH_CTM(4);
-  else if (P <= 8) LAUNCH_CTM(8);
-  else if (P <= 12) LAUNCH_CTM(12);
-  else if (P <= 16) LAUNCH_CTM(16);
-  else if (P <= 24) LAUNCH_CTM(24);
-  else if (P <= 32) LAUNCH_CTM(32);
-  else if (P <= 48) LAUNCH_CTM(48);
-  else LAUNCH_CTM(64);
-#undef LAUNCH_CTM
+  for_padded(P, [&](auto n) {
+    launch(k_col_trimmed_mean<decltype(n)::value>, grid, 0, xp, (int)P, (int)lo, (int)hi, cnt,
+           op, d, d);
+  });
 }
 
 // --------------------------------------------------------------------------- mean around
@@ -962,15 +1001,7 @@ k_col_mean_around(const float *__restrict__ x, int P, int keep, int clo, int chi
   long gstride = gridDim.x * (long)blockDim.x;
   for (; i < d; i += gstride) {
     float s[N];
-#pragma unroll
-    for (int p = 0; p < N; ++p) {
-      float v = INFINITY;
-      if (p < P) {
-        v = x[p * stride + i];
-        v = (v != v) ? INFINITY : v;
-      }
-      s[p] = v;
-    }
+    load_column(s, N, x, P, stride, i);
     sort_columns(s, std::make_integer_sequence<int, kMergeExchange<N>.n>{});
     out[i] = mean_around_sorted(s, P, keep, clo, chi, ccnt, kcnt);
   }
@@ -992,22 +1023,13 @@ void column_mean_around(torch::Tensor x, long keep, long clo, long chi, torch::T
   TORCH_CHECK(d % 4 == 0, "column_mean_around: row length must be a multiple of 4");
   if (d == 0) return;
   dim3 grid(n_blocks(d, NTHREADS));
-  hipStream_t s = cur_stream();
   const float *xp = x.data_ptr<float>();
   float *op = out.data_ptr<float>();
   float ccnt = (float)(chi - clo), kcnt = (float)keep;
-#define LAUNCH_CMA(N) \
-  hipLaunchKernelGGL((k_col_mean_around<N>), grid, dim3(NTHREADS), 0, s, xp, (int)P, \
-                     (int)keep, (int)clo, (int)chi, ccnt, kcnt, op, d, d)
-  if (P <= 4) LAUNCH_CMA(4);
-  else if (P <= 8) LAUNCH_CMA(8);
-  else if (P <= 12) LAUNCH_CMA(12);
-  else if (P <= 16) LAUNCH_CMA(16);
-  else if (P <= 24) LAUNCH_CMA(24);
-  else if (P <= 32) LAUNCH_CMA(32);
-  else if (P <= 48) LAUNCH_CMA(48);
-  else LAUNCH_CMA(64);
-#undef LAUNCH_CMA
+  for_padded(P, [&](auto n) {
+    launch(k_col_mean_around<decltype(n)::value>, grid, 0, xp, (int)P, (int)keep, (int)clo,
+           (int)chi, ccnt, kcnt, op, d, d);
+  });
 }
 
 // --------------------------------------------------------------------------- segment mean around
@@ -1018,8 +1040,8 @@ void column_mean_around(torch::Tensor x, long keep, long clo, long chi, torch::T
 //
 // Same layout as k_col_mean_around (one column per lane, grid cap, +inf padding to N,
 // register sort, mean_around_sorted); new is where the rows come from.  Per column the
-// segment is found by k_seg_wmean's binary search over the bounds staged in LDS
-// ((L+1) longs, checked against the LDS limit on the host).  The (L, T) index table is
+// segment is found by find_segment over the bounds staged in LDS ((L+1) longs, checked
+// against the LDS limit by segment_lds on the host).  The (L, T) index table is
 // NOT staged: L*T*8 bytes has no bound the host could promise (160 tensors x 64 rows is
 // 80 KiB, which would also cost occupancy), it is a few KiB that every block re-reads,
 // so it stays cache-resident and is read from global memory.  The register array s[] is
@@ -1063,7 +1085,7 @@ k_seg_mean_around(const float *__restrict__ x, const long *__restrict__ sel,
                   int chi, float ccnt, float kcnt, float *__restrict__ out, long d,
                   long stride) {
   extern __shared__ long s_seg[];
-  for (int i = threadIdx.x; i <= L; i += blockDim.x) s_seg[i] = seg[i];
+  stage_segments(s_seg, seg, L);
   __syncthreads();
   long gstride = gridDim.x * (long)blockDim.x;
   // base-indexed loop with a per-lane `valid` instead of `continue`: the sort stays in
@@ -1073,16 +1095,9 @@ k_seg_mean_around(const float *__restrict__ x, const long *__restrict__ sel,
   // (266 against 240 us at T=13).
   for (long base = blockIdx.x * (long)blockDim.x; base < d; base += gstride) {
     long i = base + threadIdx.x;
-    bool valid = (i < d) && i >= s_seg[0] && i < s_seg[L];  // false for all i when L = 0
+    bool valid = (i < d) && in_segments(s_seg, L, i);
     int lo = 0;
-    if (valid) {
-      // binary search: segment lo with seg[lo] <= i < seg[lo+1]
-      int hi = L - 1;
-      while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (s_seg[mid] <= i) lo = mid; else hi = mid - 1;
-      }
-    }
+    if (valid) lo = find_segment(s_seg, L, i);
     float s[N];
     if (valid) {
       gather_column(s, x, sel + (long)lo * T, T, P, stride, i);
@@ -1098,15 +1113,14 @@ k_seg_mean_around(const float *__restrict__ x, const long *__restrict__ sel,
 
 void segment_mean_around(torch::Tensor x, torch::Tensor sel, torch::Tensor seg, long keep,
                          long clo, long chi, torch::Tensor out) {
-  CHECK_IN(x); CHECK_IDX(sel); CHECK_IDX(seg); CHECK_IN(out);
+  CHECK_IN(x); CHECK_IDX(sel); CHECK_IN(out);
   TORCH_CHECK(x.scalar_type() == torch::kFloat32 && out.scalar_type() == torch::kFloat32,
               "segment_mean_around: x and out must be fp32");
   TORCH_CHECK(x.dim() == 2, "segment_mean_around: x must be 2D");
   TORCH_CHECK(sel.dim() == 2, "segment_mean_around: sel must be 2D (L, T)");
-  TORCH_CHECK(seg.dim() == 1 && seg.numel() >= 1,
-              "segment_mean_around: seg must be 1D with L+1 >= 1 bounds");
+  SegmentLds sl = segment_lds("segment_mean_around", seg, 0);
   long P = x.size(0), d = x.size(1), T = sel.size(1);
-  long L = seg.numel() - 1;
+  long L = sl.L;
   TORCH_CHECK(sel.size(0) == L, "segment_mean_around: sel must have one row per segment, got ",
               sel.size(0), " rows for L=", L);
   TORCH_CHECK(T >= 1 && T <= 64, "segment_mean_around kernel supports 1 <= T <= 64, got ", T);
@@ -1118,29 +1132,17 @@ void segment_mean_around(torch::Tensor x, torch::Tensor sel, torch::Tensor seg, 
               " T=", T);
   TORCH_CHECK(out.numel() == d, "segment_mean_around: out must have the length of a row of x");
   TORCH_CHECK(d % 4 == 0, "segment_mean_around: row length must be a multiple of 4");
-  size_t smem = (size_t)(L + 1) * sizeof(long);
-  TORCH_CHECK(smem <= 64 * 1024, "segment_mean_around: ", L,
-              " segment bounds do not fit the 64 KiB of LDS a block may take");
   if (d == 0) return;
   dim3 grid(n_blocks(d, NTHREADS));
-  hipStream_t s = cur_stream();
   const float *xp = x.data_ptr<float>();
   const long *sp = sel.data_ptr<long>();
   const long *gp = seg.data_ptr<long>();
   float *op = out.data_ptr<float>();
   float ccnt = (float)(chi - clo), kcnt = (float)keep;
-#define LAUNCH_SMA(N) \
-  hipLaunchKernelGGL((k_seg_mean_around<N>), grid, dim3(NTHREADS), smem, s, xp, sp, gp, (int)L, \
-                     (int)T, (int)P, (int)keep, (int)clo, (int)chi, ccnt, kcnt, op, d, d)
-  if (T <= 4) LAUNCH_SMA(4);
-  else if (T <= 8) LAUNCH_SMA(8);
-  else if (T <= 12) LAUNCH_SMA(12);
-  else if (T <= 16) LAUNCH_SMA(16);
-  else if (T <= 24) LAUNCH_SMA(24);
-  else if (T <= 32) LAUNCH_SMA(32);
-  else if (T <= 48) LAUNCH_SMA(48);
-  else LAUNCH_SMA(64);
-#undef LAUNCH_SMA
+  for_padded(T, [&](auto n) {
+    launch(k_seg_mean_around<decltype(n)::value>, grid, sl.bytes, xp, sp, gp, sl.L, (int)T,
+           (int)P, (int)keep, (int)clo, (int)chi, ccnt, kcnt, op, d, d);
+  });
 }
 
 // --------------------------------------------------------------------------- collusion
@@ -1222,26 +1224,14 @@ void collude(torch::Tensor x, std::vector<int64_t> rows, double a, double b) {
   TORCH_CHECK((uintptr_t)xp % 16 == 0, "collude: x must be 16-byte aligned");
   long d4 = d / 4;
   dim3 grid(n_blocks(d4, NTHREADS));
-  hipStream_t s = cur_stream();
   float cnt = (float)h, af = (float)a, bf = (float)b;
-#define LAUNCH_COL(N) \
-  do { \
-    if (bf != 0.f) \
-      hipLaunchKernelGGL((k_collude<N, true>), grid, dim3(NTHREADS), 0, s, xp, (int)P, mask, \
-                         cnt, af, bf, d4, d); \
-    else \
-      hipLaunchKernelGGL((k_collude<N, false>), grid, dim3(NTHREADS), 0, s, xp, (int)P, mask, \
-                         cnt, af, bf, d4, d); \
-  } while (0)
-  if (P <= 4) LAUNCH_COL(4);
-  else if (P <= 8) LAUNCH_COL(8);
-  else if (P <= 12) LAUNCH_COL(12);
-  else if (P <= 16) LAUNCH_COL(16);
-  else if (P <= 24) LAUNCH_COL(24);
-  else if (P <= 32) LAUNCH_COL(32);
-  else if (P <= 48) LAUNCH_COL(48);
-  else LAUNCH_COL(64);
-#undef LAUNCH_COL
+  for_padded(P, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if (bf != 0.f)
+      launch(k_collude<N, true>, grid, 0, xp, (int)P, mask, cnt, af, bf, d4, d);
+    else
+      launch(k_collude<N, false>, grid, 0, xp, (int)P, mask, cnt, af, bf, d4, d);
+  });
 }
 
 // --------------------------------------------------------------------------- centered clipping
@@ -1379,31 +1369,21 @@ c10::optional<torch::Tensor> clip_step(torch::Tensor x, torch::Tensor v, torch::
   TORCH_CHECK((uintptr_t)xp % 16 == 0 && (uintptr_t)vp % 16 == 0,
               "clip_step: x and v must be 16-byte aligned");
   const float *wp = w.data_ptr<float>();
-  hipStream_t s = cur_stream();
-#define LAUNCH_CLIP(N, CW) \
-  do { \
-    long nv = n / CW; \
-    int nb = n_blocks(nv, NTHREADS); \
-    if (dist) { \
-      torch::Tensor ws = torch::empty({(long)nb, P}, x.options()); \
-      hipLaunchKernelGGL((k_clip_step<N, CW, true>), dim3(nb), dim3(NTHREADS), 0, s, xp, vp, \
-                         wp, ws.data_ptr<float>(), (int)P, nv, n); \
-      hipLaunchKernelGGL(k_clip_finish, dim3((int)P), dim3(NTHREADS), 0, s, \
-                         ws.data_ptr<float>(), out->data_ptr<float>(), nb, (int)P); \
-    } else { \
-      hipLaunchKernelGGL((k_clip_step<N, CW, false>), dim3(nb), dim3(NTHREADS), 0, s, xp, vp, \
-                         wp, (float *)nullptr, (int)P, nv, n); \
-    } \
-  } while (0)
-  if (P <= 4) LAUNCH_CLIP(4, 4);
-  else if (P <= 8) LAUNCH_CLIP(8, 4);
-  else if (P <= 12) LAUNCH_CLIP(12, 4);
-  else if (P <= 16) LAUNCH_CLIP(16, 4);
-  else if (P <= 24) LAUNCH_CLIP(24, 4);
-  else if (P <= 32) LAUNCH_CLIP(32, 4);
-  else if (P <= 48) LAUNCH_CLIP(48, 2);
-  else LAUNCH_CLIP(64, 2);
-#undef LAUNCH_CLIP
+  for_padded(P, [&](auto n_pad) {
+    constexpr int N = decltype(n_pad)::value;
+    constexpr int CW = N <= 32 ? 4 : 2;  // columns per lane, see k_clip_step's comment
+    long nv = n / CW;
+    int nb = n_blocks(nv, NTHREADS);
+    if (dist) {
+      torch::Tensor ws = torch::empty({(long)nb, P}, x.options());
+      launch(k_clip_step<N, CW, true>, dim3(nb), 0, xp, vp, wp, ws.data_ptr<float>(), (int)P,
+             nv, n);
+      launch(k_clip_finish, dim3((int)P), 0, ws.data_ptr<float>(), out->data_ptr<float>(), nb,
+             (int)P);
+    } else {
+      launch(k_clip_step<N, CW, false>, dim3(nb), 0, xp, vp, wp, nullptr, (int)P, nv, n);
+    }
+  });
   return out;
 }
 
@@ -1466,13 +1446,8 @@ void worker_momentum(torch::Tensor g, torch::Tensor m, double beta, bool first) 
   int blocks = n_blocks(n4, NTHREADS);
   // 1-beta in double, then cast: 1.f - 0.99f is off by 2e-6 relative (see fused_adam_step)
   float omb = (float)(1.0 - beta);
-  hipStream_t s = cur_stream();
-  if (first)
-    hipLaunchKernelGGL((k_worker_momentum<true>), dim3(blocks), dim3(NTHREADS), 0, s,
-                       (float4 *)gp, (float4 *)mp, n4, (float)beta, omb);
-  else
-    hipLaunchKernelGGL((k_worker_momentum<false>), dim3(blocks), dim3(NTHREADS), 0, s,
-                       (float4 *)gp, (float4 *)mp, n4, (float)beta, omb);
+  launch(first ? k_worker_momentum<true> : k_worker_momentum<false>, dim3(blocks), 0,
+         (float4 *)gp, (float4 *)mp, n4, (float)beta, omb);
 }
 
 // --------------------------------------------------------------------------- module

@@ -598,6 +598,15 @@ def _sgd(p, g, buf, momentum=0.9):
 
 _I = lambda *v: torch.tensor(v, dtype=torch.int64, device=DEV)  # noqa: E731
 
+
+def _seg_over_lds():
+    """8194 bounds = 8193 segments: the bounds alone take 8194 * 8 = 65 552 B of LDS,
+    more than the 65 536 B a block may request (all segments empty but the last)."""
+    seg = torch.zeros(8194, dtype=torch.int64, device=DEV)
+    seg[-1] = 8
+    return seg
+
+
 REJECTED = {
     # length not a multiple of 4
     "sgd d%4": lambda: _sgd(_g(6), _g(6), _g(6)),
@@ -660,6 +669,18 @@ REJECTED = {
     "rows_equal int32 index": lambda: ops.rows_equal(_g(2, 8), _I(0).int(), _I(1).int(), 0.0),
     "combine_rows int32 index": lambda: ops.combine_rows(_g(3, 8), _I(0, 1).int(), _g(2), _g(8)),
     "inject unknown mode": lambda: require_extension().inject(_g(8), "bogus", False),
+    # segment bounds that do not fit the LDS of a block, and malformed x / seg
+    "segment_absmax seg over LDS": lambda: ops.segment_absmax(_g(2, 8), _seg_over_lds()),
+    "segment_pair_maxdiff seg over LDS": lambda: ops.segment_pair_maxdiff(
+        _g(2, 8), _I(0), _I(1), _seg_over_lds()),
+    "segment_sqdist seg over LDS": lambda: ops.segment_sqdist(_g(2, 8), _g(8), _seg_over_lds()),
+    "segment_weighted_mean seg over LDS": lambda: ops.segment_weighted_mean(
+        _g(2, 8), _g(2, 8193), _seg_over_lds(), _g(8)),
+    "segment_mean_around seg over LDS": lambda: ops.segment_mean_around(
+        _g(2, 8), torch.zeros(8193, 1, dtype=torch.int64, device=DEV), _seg_over_lds(), 1, 0, 1,
+        _g(8)),
+    "segment_absmax x 1D": lambda: ops.segment_absmax(_g(8), _I(0, 8)),
+    "segment_sqdist seg 2D": lambda: ops.segment_sqdist(_g(2, 8), _g(8), _I(0, 8).reshape(1, 2)),
 }
 
 
