@@ -25,9 +25,28 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..coding import CyclicCode
+from ..coding import COLLUDING_MODES, CyclicCode
 from .comm import Communicator
 from .flat import FlatSpace
+
+
+def inject_encoded_(enc: torch.Tensor, mode: str) -> None:
+    """The adversary of the cyclic approach, in place on a (2, n) view of a worker's
+    encoded (re, im) planes: the whole planes, or the [lo, hi) columns of one bucket.
+    The reference injects on the encoded complex combination with cyclic=True
+    (additive error, cyclic_worker.py:181-183 / model_ops/utils.py:8-11).  Every mode
+    but gauss is per element, so slices compose to the whole; gauss scales its noise by
+    the mean magnitude of the view it is given."""
+    if mode == "rev_grad":
+        enc.add_(enc, alpha=ops.fallback.ADVERSARY_)
+    elif mode == "constant":
+        enc[0].add_(ops.fallback.ADVERSARY_)
+    elif mode in ("random", "none", ""):
+        pass
+    elif mode == "gauss":
+        enc.add_(torch.randn_like(enc) * enc.abs().mean().clamp(min=1e-12) * 100.0)
+    else:
+        raise ValueError(mode)
 
 
 class Aggregator:
@@ -44,6 +63,11 @@ class Aggregator:
     # honest rows only after the exchange, so they act inside exchanged().  The trainer
     # sets collusion.rows from the host-side schedule before every aggregate().
     collusion = None
+    # the most rows the rule's HIP kernel holds (None: no limit) and why; _check_rows
+    # is the CPU-side config check, so a bad count fails at construction and not at
+    # the first kernel launch on the GPU
+    MAX_WORKERS = None
+    MAX_WORKERS_WHY = ""
 
     def __init__(self, comm: Communicator, space: FlatSpace, comm_dtype=torch.float32):
         self.comm = comm
@@ -126,17 +150,28 @@ class Aggregator:
             ops.collude_(recv, col.rows, col.a, col.b)
         return recv
 
-    def _exchange(self, payload: torch.Tensor) -> torch.Tensor:
-        rows = payload.shape[0]
-        if not self.comm.distributed:
-            return payload.view(rows, self.space.shard)
-        for r in range(rows):
+    def _check_rows(self, P: int) -> None:
+        if self.MAX_WORKERS is not None and P > self.MAX_WORKERS:
+            raise ValueError(f"{self.name} supports at most {self.MAX_WORKERS} workers "
+                             f"(got {P}): {self.MAX_WORKERS_WHY}")
+
+    def _start_rest(self, payload: torch.Tensor) -> None:
+        for r in range(payload.shape[0]):
             if r not in self._started:
                 self.start_row(payload, r)
+
+    def _drain(self) -> None:
         for w in self._works:
             w.wait()
         self._works = []
         self._started = set()
+
+    def _exchange(self, payload: torch.Tensor) -> torch.Tensor:
+        rows = payload.shape[0]
+        if not self.comm.distributed:
+            return payload.view(rows, self.space.shard)
+        self._start_rest(payload)
+        self._drain()
         for tmp2d, row, slo, shi in self._pending_copies:
             self._recv[row, :, slo:shi].copy_(tmp2d)
         self._pending_copies = []
@@ -199,21 +234,13 @@ class MeanAggregator(Aggregator):
             self._out /= float(self.num_workers)
             return self._out
         if self._bucketed:
-            for w in self._works:
-                w.wait()
-            self._works = []
-            self._started = set()
+            self._drain()
             self._bucketed = False
             ops.sum_rows(payload, self._out)  # rows now hold cross-rank sums
             self._out /= float(self.num_workers)
             return self._out
-        for r in range(payload.shape[0]):
-            if r not in self._started:
-                self.start_row(payload, r)
-        for w in self._works:
-            w.wait()
-        self._works = []
-        self._started = set()
+        self._start_rest(payload)
+        self._drain()
         torch.sum(self._rs_shards, dim=0, out=self._shard_out)
         self._shard_out /= float(self.num_workers)
         self.comm.all_gather_shard(self._shard_out, self._out)
@@ -505,18 +532,14 @@ class KrumAggregator(Aggregator):
     """
 
     name = "krum"
+    MAX_WORKERS = 32  # the k_seg_gram LDS tile (draco_kernels.hip GRAM_CHUNK layout)
+    MAX_WORKERS_WHY = "the segment-Gram HIP kernel stages a (P, chunk) LDS tile sized for P <= 32"
 
     def __init__(self, comm, space, num_workers: int, s: int):
         super().__init__(comm, space)
         self.num_workers = num_workers
         self.s = s
-        if num_workers > 32:
-            # CPU-side config check: the k_seg_gram LDS tile is sized for P <= 32
-            # (draco_kernels.hip GRAM_CHUNK layout); fail at construction, not at
-            # first kernel launch on the GPU
-            raise ValueError(
-                f"KrumAggregator supports at most 32 workers (got {num_workers}): "
-                "the segment-Gram HIP kernel stages a (P, chunk) LDS tile sized for P <= 32")
+        self._check_rows(num_workers)
         # per-column segment id of the local shard (for device-side winner assembly:
         # out[c] = recv[winner[seg_of(c)], c]); zero-length padding tail maps to 0
         # and is zeroed after the gather
@@ -553,14 +576,15 @@ class _KrumSelectAggregator(Aggregator):
     through the per-segment index table), all_gather.  last_sel keeps the (L, T)
     selection of the latest call, on device."""
 
-    MAX_WORKERS = 32  # the segment-Gram HIP kernel stages a (P, chunk) LDS tile for P <= 32
+    MAX_WORKERS = KrumAggregator.MAX_WORKERS
+    MAX_WORKERS_WHY = KrumAggregator.MAX_WORKERS_WHY
 
     def __init__(self, comm, space, num_workers: int, f: int):
         super().__init__(comm, space)
         self.num_workers = num_workers
         self.f = f
         self.last_sel = None
-        self._plan(num_workers)  # CPU-side config check: fail at construction
+        self._plan(num_workers)  # config check: fail at construction
 
     def _plan(self, P: int):
         raise NotImplementedError
@@ -568,10 +592,7 @@ class _KrumSelectAggregator(Aggregator):
     def _check_workers(self, P: int, need: int, why: str) -> None:
         if self.f < 0:
             raise ValueError(f"f must be >= 0, got {self.f}")
-        if P > self.MAX_WORKERS:
-            raise ValueError(
-                f"{self.name} supports at most {self.MAX_WORKERS} workers (got {P}): "
-                "the segment-Gram HIP kernel stages a (P, chunk) LDS tile sized for P <= 32")
+        self._check_rows(P)
         if P < need:
             raise ValueError(
                 f"{self.name} with f={self.f} needs at least {why} = {need} workers, got {P}")
@@ -664,22 +685,6 @@ class BulyanAggregator(_KrumSelectAggregator):
                 theta // 2 + 1)
 
 
-BASELINE_MODES = ("normal/geometric_median/krum/median/trimmed_mean/meamed/phocas/"
-                  "multi_krum/bulyan/centered_clip")
-
-
-def krum_select_aggregator(mode: str, comm, space, num_workers: int, f: int):
-    """mode = multi_krum | bulyan with f = worker_fail (Trainer and PS master).  These
-    two rules have a floor on the worker count (2f+3, 4f+3) that a default
-    one-worker-per-rank configuration misses, so a configuration they cannot run at is
-    reported together with the modes one can switch to."""
-    cls = MultiKrumAggregator if mode == "multi_krum" else BulyanAggregator
-    try:
-        return cls(comm, space, num_workers=num_workers, f=f)
-    except ValueError as e:
-        raise ValueError(f"{e} (baseline approach supports modes {BASELINE_MODES})") from None
-
-
 class TrimmedMeanAggregator(Aggregator):
     """Coordinate-wise median / beta-trimmed mean (arXiv:1803.01498), sharded over d.
 
@@ -695,19 +700,15 @@ class TrimmedMeanAggregator(Aggregator):
     the trainer's nan-guard then skips the update.)
     """
 
-    MAX_WORKERS = 64  # the kernel sorts a column in registers, padded to <= 64 rows
+    MAX_WORKERS = 64  # padded to <= 64 rows
+    MAX_WORKERS_WHY = "the column-sort HIP kernel holds a column in registers"
 
     def __init__(self, comm, space, num_workers: int, trim: int | None = None):
         super().__init__(comm, space)
         self.num_workers = num_workers
         self.trim = trim
         self.name = "median" if trim is None else "trimmed_mean"
-        if num_workers > self.MAX_WORKERS:
-            # CPU-side config check (as for Krum): fail at construction, not at the
-            # first kernel launch on the GPU
-            raise ValueError(
-                f"TrimmedMeanAggregator supports at most {self.MAX_WORKERS} workers "
-                f"(got {num_workers}): the column-sort HIP kernel holds a column in registers")
+        self._check_rows(num_workers)
         if trim is not None and trim < 0:
             raise ValueError(f"trim must be >= 0, got {trim}")
         self._bounds(num_workers)
@@ -753,7 +754,8 @@ class MeanAroundAggregator(Aggregator):
     then skips the update.)
     """
 
-    MAX_WORKERS = 64  # the kernel sorts a column in registers, padded to <= 64 rows
+    MAX_WORKERS = TrimmedMeanAggregator.MAX_WORKERS
+    MAX_WORKERS_WHY = TrimmedMeanAggregator.MAX_WORKERS_WHY
 
     def __init__(self, comm, space, num_workers: int, b: int, center: str = "median"):
         super().__init__(comm, space)
@@ -763,11 +765,7 @@ class MeanAroundAggregator(Aggregator):
         self.b = b
         self.center = center
         self.name = "meamed" if center == "median" else "phocas"
-        if num_workers > self.MAX_WORKERS:
-            # CPU-side config check: fail at construction, not at the first launch
-            raise ValueError(
-                f"MeanAroundAggregator supports at most {self.MAX_WORKERS} workers "
-                f"(got {num_workers}): the column-sort HIP kernel holds a column in registers")
+        self._check_rows(num_workers)
         self._bounds(num_workers)
 
     def _bounds(self, P: int):
@@ -830,15 +828,12 @@ class CenteredClipAggregator(Aggregator):
     """
 
     name = "centered_clip"
-    MAX_WORKERS = 64  # the clip-step HIP kernel holds a column in registers, <= 64 rows
+    MAX_WORKERS = 64
+    MAX_WORKERS_WHY = "the clip-step HIP kernel holds a column in registers"
 
     def __init__(self, comm, space, num_workers: int, tau: float = 0.0, iters: int = 3):
         super().__init__(comm, space)
-        if num_workers > self.MAX_WORKERS:
-            # CPU-side config check: fail at construction, not at the first launch
-            raise ValueError(
-                f"CenteredClipAggregator supports at most {self.MAX_WORKERS} workers "
-                f"(got {num_workers}): the clip-step HIP kernel holds a column in registers")
+        self._check_rows(num_workers)
         if iters < 1:
             raise ValueError(f"centered_clip needs iters >= 1, got {iters}")
         self.num_workers = num_workers
@@ -852,12 +847,10 @@ class CenteredClipAggregator(Aggregator):
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
         recv = self.exchanged(payload)  # (P, shard)
-        P = recv.shape[0]  # per call: the survivor world has fewer rows
-        if P > self.MAX_WORKERS:
-            raise ValueError(f"centered_clip supports at most {self.MAX_WORKERS} rows, got {P}")
-        shard = self.space.shard
+        P = recv.shape[0]  # per call: the survivor world is rebuilt, but this reaches the kernel
+        self._check_rows(P)
         v = self._shard_out
-        v.copy_(self._out[self.comm.rank * shard:(self.comm.rank + 1) * shard])
+        v.copy_(self.space.shard_of(self._out, self.comm.rank))
         inf = float("inf")
         d2 = ops.clip_step_(recv, v, torch.zeros(P, dtype=torch.float32, device=recv.device))
         tau = self.tau
@@ -949,3 +942,50 @@ class CyclicAggregator(Aggregator):
         ops.combine_rows(recv, self._alive_rows, w, self._shard_out)
         self.comm.all_gather_shard(self._shard_out, self._out)
         return self._out
+
+
+# ------------------------------------------------------------------ baseline rule table
+# mode -> (class, cfg -> rule arguments), shared by Trainer and the PS master.  The
+# count a rule tolerates (Krum's s, the trim per end, b, f) is cfg.worker_fail.
+_BASELINE_RULES = {
+    "normal": (MeanAggregator, lambda cfg: {}),
+    "geometric_median": (GeoMedianAggregator, lambda cfg: {}),
+    "krum": (KrumAggregator, lambda cfg: {"s": cfg.worker_fail}),
+    "median": (TrimmedMeanAggregator, lambda cfg: {}),
+    "trimmed_mean": (TrimmedMeanAggregator, lambda cfg: {"trim": cfg.worker_fail}),
+    "meamed": (MeanAroundAggregator, lambda cfg: {"b": cfg.worker_fail, "center": "median"}),
+    "phocas": (MeanAroundAggregator,
+               lambda cfg: {"b": cfg.worker_fail, "center": "trimmed_mean"}),
+    "multi_krum": (MultiKrumAggregator, lambda cfg: {"f": cfg.worker_fail}),
+    "bulyan": (BulyanAggregator, lambda cfg: {"f": cfg.worker_fail}),
+    "centered_clip": (CenteredClipAggregator,
+                      lambda cfg: {"tau": cfg.clip_tau, "iters": cfg.clip_iters}),
+}
+BASELINE_MODES = "/".join(_BASELINE_RULES)
+
+
+def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
+    """The baseline approach's rule for cfg.mode over num_workers logical workers."""
+    if cfg.mode not in _BASELINE_RULES:
+        raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, got {cfg.mode!r}")
+    cls, args = _BASELINE_RULES[cfg.mode]
+    kwargs, name, hint = args(cfg), None, ""
+    if cfg.mode == "normal" and cfg.err_mode in COLLUDING_MODES:
+        # MeanAggregator sums inside the reduce-scatter: the honest rows are never
+        # visible together.  Under a colluding adversary the plain mean goes over
+        # the exchange path instead: the trimmed mean with nothing trimmed.
+        cls, kwargs, name = TrimmedMeanAggregator, {"trim": 0}, "mean"
+        hint = (f" (mode 'normal' under the colluding err mode {cfg.err_mode!r} is the "
+                "trim=0 mean over the exchange path, so that kernel's limit of 64 workers "
+                "applies)")
+    elif cfg.mode in ("multi_krum", "bulyan"):
+        # these two have a floor on the worker count (2f+3, 4f+3) that a default
+        # one-worker-per-rank configuration misses: name the modes one can switch to
+        hint = f" (baseline approach supports modes {BASELINE_MODES})"
+    try:
+        agg = cls(comm, space, num_workers=num_workers, **kwargs)
+    except ValueError as e:
+        raise ValueError(f"{e}{hint}") from None
+    if name is not None:
+        agg.name = name
+    return agg

@@ -103,22 +103,13 @@ class Communicator:
     def reduce_scatter_row(self, payload_row: torch.Tensor, out_shard: torch.Tensor,
                            async_op: bool = False):
         """payload_row (d_pad,) -> out_shard (shard,) = global sum of this rank's
-        shard of the row.  The overlap-capable form of reduce_scatter_sum: the
-        trainer posts one per payload row as its backward completes."""
+        shard of the row.  Overlap-capable: the trainer posts one per payload row as
+        its backward completes."""
         if not self.distributed:
             out_shard.copy_(payload_row)
             return None
         work = dist.reduce_scatter_tensor(out_shard, payload_row, group=self.group, async_op=async_op)
         return work if async_op else None
-
-    def reduce_scatter_sum(self, payload_sum: torch.Tensor) -> torch.Tensor:
-        """payload_sum: (d_pad,) local sum -> (shard,) global sum of this rank's shard."""
-        shard = payload_sum.shape[0] // self.world
-        if not self.distributed:
-            return payload_sum
-        out = torch.empty(shard, dtype=payload_sum.dtype, device=payload_sum.device)
-        dist.reduce_scatter_tensor(out, payload_sum, group=self.group)
-        return out
 
     def all_gather_shard(self, shard: torch.Tensor, out: torch.Tensor) -> None:
         """shard: (shard,) -> out: (d_pad,) gathered from all ranks."""
@@ -156,12 +147,6 @@ class Communicator:
     # ------------------------------------------------------------------ p2p (PS mode)
     def send(self, t: torch.Tensor, dst: int, tag: int = 0):
         dist.send(t, dst=dst, tag=tag)
-
-    def recv(self, t: torch.Tensor, src: int, tag: int = 0):
-        dist.recv(t, src=src, tag=tag)
-
-    def isend(self, t: torch.Tensor, dst: int, tag: int = 0):
-        return dist.isend(t, dst=dst, tag=tag)
 
     def irecv(self, t: torch.Tensor, src: int, tag: int = 0):
         return dist.irecv(t, src=src, tag=tag)

@@ -37,8 +37,8 @@ class HealthMonitor:
     """Heartbeats run on a BACKGROUND daemon thread (every timeout/4), so a rank
     busy in a long step (MIOpen find / graph capture can take minutes) still beats
     — only a DEAD process stops.  A hung-but-alive rank is therefore not detected
-    here (that is the PS lane's timeout-as-erasure job, ps.py:203-275); this lane
-    handles process death, which is what hangs the reference forever."""
+    here (that is the PS lane's timeout-as-erasure job, ps.py Master._gather_grads);
+    this lane handles process death, which is what hangs the reference forever."""
 
     def __init__(self, rank: int, world: int, timeout: float):
         self.rank = rank

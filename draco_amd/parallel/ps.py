@@ -29,41 +29,14 @@ from ..optim import FlatSGD
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
 from .aggregators import (
-    BASELINE_MODES,
-    CenteredClipAggregator,
     CyclicAggregator,
-    GeoMedianAggregator,
-    KrumAggregator,
-    MeanAggregator,
-    MeanAroundAggregator,
-    TrimmedMeanAggregator,
     VoteAggregator,
-    krum_select_aggregator,
+    build_baseline_aggregator,
+    inject_encoded_,
 )
 from .comm import Communicator
 from .flat import FlatSpace
 from .trainer import _resolve_device
-
-
-class _LocalComm:
-    """World-1 stand-in so the sharded aggregators run unsharded on the PS."""
-
-    rank = 0
-    world = 1
-    distributed = False
-
-    def all_to_all_rows(self, payload):
-        L, d = payload.shape
-        return payload.view(L, d)
-
-    def reduce_scatter_sum(self, x):
-        return x
-
-    def all_gather_shard(self, shard, out):
-        out.copy_(shard)
-
-    def all_reduce(self, t, op="sum"):
-        return t
 
 
 class _PSBase:
@@ -127,32 +100,10 @@ class Master(_PSBase):
         super().__init__(cfg)
         assert self.rank == 0
         self.opt = FlatSGD(self.space.flat_param, lr=cfg.lr, momentum=cfg.momentum)
-        local = _LocalComm()
+        # a world-1 communicator: the sharded aggregators run unsharded on the PS
+        local = Communicator(0, 1, self.device)
         if cfg.approach == "baseline":
-            if cfg.mode == "normal":
-                self.agg = MeanAggregator(local, self.space, num_workers=self.P)
-            elif cfg.mode == "geometric_median":
-                self.agg = GeoMedianAggregator(local, self.space, num_workers=self.P)
-            elif cfg.mode == "krum":
-                self.agg = KrumAggregator(local, self.space, num_workers=self.P, s=cfg.worker_fail)
-            elif cfg.mode == "median":
-                self.agg = TrimmedMeanAggregator(local, self.space, num_workers=self.P)
-            elif cfg.mode == "trimmed_mean":
-                self.agg = TrimmedMeanAggregator(local, self.space, num_workers=self.P,
-                                                 trim=cfg.worker_fail)
-            elif cfg.mode in ("meamed", "phocas"):
-                self.agg = MeanAroundAggregator(
-                    local, self.space, num_workers=self.P, b=cfg.worker_fail,
-                    center="median" if cfg.mode == "meamed" else "trimmed_mean")
-            elif cfg.mode in ("multi_krum", "bulyan"):
-                self.agg = krum_select_aggregator(cfg.mode, local, self.space, self.P,
-                                                  cfg.worker_fail)
-            elif cfg.mode == "centered_clip":
-                self.agg = CenteredClipAggregator(local, self.space, num_workers=self.P,
-                                                  tau=cfg.clip_tau, iters=cfg.clip_iters)
-            else:
-                raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, "
-                                 f"got {cfg.mode!r}")
+            self.agg = build_baseline_aggregator(cfg, local, self.space, self.P)
         elif cfg.approach == "maj_vote":
             r = cfg.group_size
             if self.P % r != 0:
@@ -381,7 +332,7 @@ class Worker(_PSBase):
                     losses.append(self._fwd_bwd(x, y, self.scratch[k]))
                 ops.cyclic_encode(self.scratch, self._w_re, self._w_im, self.payload)
                 if self.worker_id in adversaries:
-                    _inject_encoded(self.payload, cfg.err_mode)
+                    inject_encoded_(self.payload, cfg.err_mode)
                 loss = float(np.mean(losses)) if losses else float("nan")
             else:
                 x, y = self.data.batch_for(self.group, self.step_num)
@@ -409,17 +360,6 @@ class Worker(_PSBase):
         loss = self.criterion(logits, y)
         loss.backward()
         return float(loss.detach())
-
-
-def _inject_encoded(enc, mode):
-    if mode == "rev_grad":
-        enc.add_(enc, alpha=ops.fallback.ADVERSARY_)
-    elif mode == "constant":
-        enc[0].add_(ops.fallback.ADVERSARY_)
-    elif mode in ("random", "none", ""):
-        pass
-    else:
-        raise ValueError(mode)
 
 
 def run_ps(cfg: Config, max_steps: int | None = None):

@@ -38,19 +38,14 @@ from ..optim import FlatSGD
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.logging import MetricsLogger
 from .aggregators import (
-    BASELINE_MODES,
-    CenteredClipAggregator,
     CyclicAggregator,
-    GeoMedianAggregator,
-    KrumAggregator,
-    MeanAggregator,
-    MeanAroundAggregator,
-    TrimmedMeanAggregator,
     VoteAggregator,
-    krum_select_aggregator,
+    build_baseline_aggregator,
+    inject_encoded_,
 )
 from .comm import Communicator
 from .flat import FlatSpace
+from .worker_momentum import WorkerMomentum
 
 
 def _resolve_device(cfg: Config, rank: int) -> torch.device:
@@ -194,16 +189,10 @@ class Trainer:
             raise ValueError(f"unknown approach {approach!r}")
         self._setup_decode()
 
-        # ---------------- worker-side momentum (arXiv:2012.10333) ----------------
-        # Every local logical worker keeps a private fp32 state row and sends its
-        # momentum instead of its gradient (ops.worker_momentum_); off (no buffer,
-        # no call) at the default beta = 0.  The adversary injection acts on the
-        # sent row only, so every slot keeps an HONEST state: the schedule picks
-        # different Byzantine workers every step.
-        self._wm_beta = float(cfg.worker_momentum)
-        if self._wm_beta > 0.0:
-            self._wm = self.space.alloc_payload(self.L)
-            self._wm_first = [True] * self.L
+        # worker-side momentum (parallel/worker_momentum.py); off (no buffer, no
+        # call) at the default beta = 0
+        self.wm = (WorkerMomentum(self.space, self.L, cfg.worker_momentum)
+                   if cfg.worker_momentum > 0.0 else None)
 
         self.use_graphs = bool(cfg.hip_graphs) and device.type == "cuda" and not cfg.deterministic
         self._graphs = {}
@@ -270,47 +259,6 @@ class Trainer:
         return SyntheticClassification(self.cfg.dataset, self.device, seed=1234,
                                        task=self.cfg.synthetic_task)
 
-    def _baseline_aggregator(self, cfg: Config, num_workers: int):
-        if cfg.mode == "normal" and cfg.err_mode in COLLUDING_MODES:
-            # MeanAggregator sums inside the reduce-scatter: the honest rows are never
-            # visible together.  Under a colluding adversary the plain mean goes over
-            # the exchange path instead: the trimmed mean with nothing trimmed.
-            try:
-                agg = TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers,
-                                            trim=0)
-            except ValueError as e:
-                raise ValueError(
-                    f"{e} (mode 'normal' under the colluding err mode {cfg.err_mode!r} is "
-                    "the trim=0 mean over the exchange path, so that kernel's limit of 64 "
-                    "workers applies)") from None
-            agg.name = "mean"
-            return agg
-        if cfg.mode == "normal":
-            return MeanAggregator(self.comm, self.space, num_workers=num_workers)
-        if cfg.mode == "geometric_median":
-            return GeoMedianAggregator(self.comm, self.space, num_workers=num_workers)
-        if cfg.mode == "krum":
-            return KrumAggregator(self.comm, self.space, num_workers=num_workers, s=cfg.worker_fail)
-        if cfg.mode == "median":
-            return TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers)
-        if cfg.mode == "trimmed_mean":
-            # trim = the tolerated adversary count, as Krum takes s = worker_fail
-            return TrimmedMeanAggregator(self.comm, self.space, num_workers=num_workers,
-                                         trim=cfg.worker_fail)
-        if cfg.mode in ("meamed", "phocas"):
-            # b = the tolerated adversary count; the centre is the median / b-trimmed mean
-            return MeanAroundAggregator(
-                self.comm, self.space, num_workers=num_workers, b=cfg.worker_fail,
-                center="median" if cfg.mode == "meamed" else "trimmed_mean")
-        if cfg.mode in ("multi_krum", "bulyan"):
-            # f = the tolerated adversary count, as Krum takes s = worker_fail
-            return krum_select_aggregator(cfg.mode, self.comm, self.space, num_workers,
-                                          cfg.worker_fail)
-        if cfg.mode == "centered_clip":
-            return CenteredClipAggregator(self.comm, self.space, num_workers=num_workers,
-                                          tau=cfg.clip_tau, iters=cfg.clip_iters)
-        raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, got {cfg.mode!r}")
-
     def _setup_decode(self) -> None:
         """Build the aggregator + comm-layout buffers for the CURRENT communicator
         (called at init, and again with the survivor communicator after a rank
@@ -318,7 +266,8 @@ class Trainer:
         cfg = self.cfg
         alive = self.health.alive if self.health is not None else list(range(self.world))
         if self.approach == "baseline":
-            self.agg = self._baseline_aggregator(cfg, num_workers=self.L * len(alive))
+            self.agg = build_baseline_aggregator(cfg, self.comm, self.space,
+                                                 self.L * len(alive))
             self.payload = self.space.alloc_payload(self.L)
             if cfg.err_mode in COLLUDING_MODES:
                 # colluding adversaries act on the exchanged block, inside aggregate()
@@ -389,16 +338,10 @@ class Trainer:
         self.comm.broadcast(self.space.flat_param, src=src)
         for name in stash:
             self.comm.broadcast(getattr(self.opt, name), src=src)
-        bufs = [b for b in self.model.buffers() if b.dtype.is_floating_point]
-        if bufs:
-            flatb = torch.cat([b.reshape(-1).float() for b in bufs])
+        flatb = self._float_buffers()
+        if flatb is not None:
             self.comm.broadcast(flatb, src=src)
-            off = 0
-            with torch.no_grad():
-                for b in bufs:
-                    n = b.numel()
-                    b.copy_(flatb[off : off + n].view(b.shape).to(b.dtype))
-                    off += n
+            self._set_float_buffers(flatb)
         meta = torch.tensor([self.step_num], dtype=torch.int64,
                             device=self.device if self.comm.backend == "nccl" else "cpu")
         self.comm.broadcast(meta, src=src)
@@ -409,15 +352,15 @@ class Trainer:
             x = x.to(memory_format=torch.channels_last)
         self.space.attach_grads(grad_row)
         grad_row.zero_()
-        if self.autocast_dtype is not None:
-            with torch.autocast("cuda", dtype=self.autocast_dtype):
-                logits = self.model(x)
-                loss = self.criterion(logits, y)
-        else:
-            logits = self.model(x)
-            loss = self.criterion(logits, y)
+        loss = self._loss(x, y)
         loss.backward()
         return loss.detach()
+
+    def _loss(self, x, y):
+        if self.autocast_dtype is not None:
+            with torch.autocast("cuda", dtype=self.autocast_dtype):
+                return self.criterion(self.model(x), y)
+        return self.criterion(self.model(x), y)
 
     # ------------------------------------------------------------ bucketed overlap
     def _make_bucket_hook(self, pidx: int):
@@ -433,15 +376,15 @@ class Trainer:
         return hook
 
     def _ship_bucket(self, bi: int) -> None:
-        if self._hook_row == "cyclic":
-            self._ship_bucket_cyclic(bi)
-            return
         lo, hi, _ = self._buckets[bi]
+        if self._hook_row == "cyclic":
+            for l in range(self.L):
+                self._encode_and_ship(l, lo, hi)
+            return
         row = self._hook_row
-        if self._wm_beta > 0.0:
+        if self.wm is not None:
             # the chunk is final (build_buckets): momentum first, then the injection
-            ops.worker_momentum_(self.payload[row, lo:hi], self._wm[row, lo:hi],
-                                 self._wm_beta, self._wm_first[row])
+            self.wm.apply(self.payload, row, lo, hi)
         if self._hook_adversary:
             # injection at the send boundary, per chunk — same placement as the
             # reference's per-layer err_simulation inside backward (lenet.py:129-141)
@@ -453,48 +396,33 @@ class Trainer:
     # backward — when bucket b of that backward lands, bucket b of every earlier
     # sub-batch is long final, so the bucket's slice of each logical worker's
     # encoded planes is computed, injected, and shipped while the rest of the
-    # last backward still runs.
-    def _ship_bucket_cyclic(self, bi: int) -> None:
-        lo, hi, _ = self._buckets[bi]
-        n = hi - lo
-        for l in range(self.L):
-            w_global = l * self.world + self.rank
-            enc = self.payload[2 * l : 2 * l + 2]
-            ops.combine_rows_slice(self.scratch, self._enc_rows[l], self._w_re[l],
-                                   enc[0, lo:hi], lo)
-            ops.combine_rows_slice(self.scratch, self._enc_rows[l], self._w_im[l],
-                                   enc[1, lo:hi], lo)
-            if w_global in self._cyc_advs:
-                self._inject_encoded_slice(enc, lo, hi, self.cfg.err_mode)
-            self.agg.start_bucket(self.payload, 2 * l, lo, hi)
-            self.agg.start_bucket(self.payload, 2 * l + 1, lo, hi)
+    # last backward still runs.  Without buckets the same routine runs once per
+    # logical worker over the whole row, after the last backward.
+    def _encode_and_ship(self, l: int, lo: int, hi: int) -> None:
+        """Encode the [lo, hi) columns of logical worker l's band (gathered scratch
+        rows) into its (re, im) payload planes, inject, start the exchange."""
+        enc = self.payload[2 * l : 2 * l + 2]
+        for plane, w in enumerate((self._w_re[l], self._w_im[l])):
+            ops.combine_rows_slice(self.scratch, self._enc_rows[l], w, enc[plane, lo:hi], lo)
+        if l * self.world + self.rank in self._cyc_advs:
+            inject_encoded_(enc[:, lo:hi], self.cfg.err_mode)
+        for row in (2 * l, 2 * l + 1):
+            if self.use_buckets:
+                self.agg.start_bucket(self.payload, row, lo, hi)
+            else:
+                self.agg.start_row(self.payload, row)
 
-    def _begin_cyclic_buckets(self, adversaries) -> None:
+    def _begin_cyclic_buckets(self) -> None:
         self._bucket_left = [len(b[2]) for b in self._buckets]
-        self._cyc_advs = adversaries
         self._hook_row = "cyclic"
 
     def _end_cyclic_buckets(self) -> None:
         for bi, left in enumerate(self._bucket_left):
             if left > 0:
-                self._ship_bucket_cyclic(bi)
-        for l in range(self.L):
-            self.agg.mark_row_started(2 * l)
-            self.agg.mark_row_started(2 * l + 1)
+                self._ship_bucket(bi)
+        for row in range(2 * self.L):
+            self.agg.mark_row_started(row)
         self._hook_row = None
-
-    def _inject_encoded_slice(self, enc: torch.Tensor, lo: int, hi: int, mode: str) -> None:
-        s = enc[:, lo:hi]
-        if mode == "rev_grad":
-            s.add_(s, alpha=ops.fallback.ADVERSARY_)
-        elif mode == "constant":
-            enc[0, lo:hi].add_(ops.fallback.ADVERSARY_)
-        elif mode in ("random", "none", ""):
-            pass
-        elif mode == "gauss":
-            s.add_(torch.randn_like(s) * s.abs().mean().clamp(min=1e-12) * 100.0)
-        else:
-            raise ValueError(mode)
 
     def _inject_row(self, row: int, lo: int, hi: int) -> None:
         if self.cfg.err_mode in COLLUDING_MODES:
@@ -531,8 +459,8 @@ class Trainer:
             if left > 0:
                 self._ship_bucket(bi)
         self.agg.mark_row_started(self._hook_row)
-        if self._wm_beta > 0.0:
-            self._wm_first[self._hook_row] = False  # only now has the whole row shipped
+        if self.wm is not None:
+            self.wm.row_sent(self._hook_row)  # only now has the whole row shipped
         self._hook_row = None
 
     # ------------------------------------------------------------ hipGraph capture
@@ -603,11 +531,7 @@ class Trainer:
 
         def body():
             grad_row.zero_()
-            if self.autocast_dtype is not None:
-                with torch.autocast("cuda", dtype=self.autocast_dtype):
-                    loss = self.criterion(self.model(static_x), static_y)
-            else:
-                loss = self.criterion(self.model(static_x), static_y)
+            loss = self._loss(static_x, static_y)
             loss.backward()
             return loss
 
@@ -659,12 +583,11 @@ class Trainer:
         if self.approach in ("baseline", "maj_vote"):
             pending = []
             for l in range(self.L):
+                worker_id = l * self.world + self.rank  # l-major global worker id
                 if self.approach == "baseline":
-                    worker_id = l * self.world + self.rank  # l-major global worker id
                     group = worker_id  # every worker draws its own stream
                 else:
                     group = (self.rank - l) % self.world
-                    worker_id = l * self.world + self.rank  # l-major global worker id
                 x, y = self.data.batch_for(group, step)
                 if self.use_buckets:
                     # per-layer overlap: hooks ship ~bucket_mb chunks of this row
@@ -679,26 +602,26 @@ class Trainer:
             for l, worker_id, st in pending:
                 if st is not None:  # order the default stream after worker l's graph
                     torch.cuda.current_stream().wait_stream(st)
-                if self._wm_beta > 0.0:
+                if self.wm is not None:
                     # outside the captured graph: capture runs body() during its
                     # warm-up, which would advance the state
-                    ops.worker_momentum_(self.payload[l], self._wm[l], self._wm_beta,
-                                         self._wm_first[l])
-                    self._wm_first[l] = False
+                    self.wm.apply(self.payload, l, 0, self.space.d_pad)
+                    self.wm.row_sent(l)
                 if worker_id in adversaries:
                     self._inject_row(l, 0, self.space.d_pad)
                 # overlap: this row's all_to_all runs while other backwards compute
                 self.agg.start_row(self.payload, l)
         else:  # cyclic
             # phase 1: every DISTINCT local sub-batch fwd/bwd replays concurrently
+            self._cyc_advs = adversaries
             streams = []
             last = len(self._local_subs) - 1
             for i, j in enumerate(self._local_subs):
                 x, y = self.data.sub_batch(j, step)
                 if self.use_buckets and i == last:
                     # per-layer overlap: bucketed encode+exchange fires from the
-                    # last sub-batch's backward hooks (see _ship_bucket_cyclic)
-                    self._begin_cyclic_buckets(adversaries)
+                    # last sub-batch's backward hooks (see _encode_and_ship)
+                    self._begin_cyclic_buckets()
                     losses.append(self._forward_backward(x, y, self.scratch[i]))
                     self._end_cyclic_buckets()
                     break
@@ -712,14 +635,7 @@ class Trainer:
                 # phase 2: per logical worker, encode its band (gathered rows),
                 # inject, start the exchange
                 for l in range(self.L):
-                    w_global = l * self.world + self.rank
-                    enc = self.payload[2 * l : 2 * l + 2]
-                    ops.combine_rows(self.scratch, self._enc_rows[l], self._w_re[l], enc[0])
-                    ops.combine_rows(self.scratch, self._enc_rows[l], self._w_im[l], enc[1])
-                    if w_global in adversaries:
-                        self._inject_encoded(enc, cfg.err_mode)
-                    self.agg.start_row(self.payload, 2 * l)
-                    self.agg.start_row(self.payload, 2 * l + 1)
+                    self._encode_and_ship(l, 0, self.space.d_pad)
 
         t_comp = time.perf_counter()
         ev_comp = self._event()
@@ -776,20 +692,6 @@ class Trainer:
         self.logger.log(rec)
         return rec
 
-    def _inject_encoded(self, enc: torch.Tensor, mode: str) -> None:
-        # reference injects on the encoded complex combination with cyclic=True
-        # (additive error, cyclic_worker.py:181-183 / model_ops/utils.py:8-11)
-        if mode == "rev_grad":
-            enc.add_(enc, alpha=ops.fallback.ADVERSARY_)
-        elif mode == "constant":
-            enc[0].add_(ops.fallback.ADVERSARY_)
-        elif mode in ("random", "none", ""):
-            pass
-        elif mode == "gauss":
-            enc.add_(torch.randn_like(enc) * enc.abs().mean().clamp(min=1e-12) * 100.0)
-        else:
-            raise ValueError(mode)
-
     # ------------------------------------------------------------------ eval / io
     @torch.no_grad()
     def evaluate(self, n_batches: int = 8) -> dict:
@@ -821,73 +723,42 @@ class Trainer:
         own group batches; parameters stay bit-identical by construction)."""
         if not self.comm.distributed:
             return
-        bufs = [b for b in self.model.buffers() if b.dtype.is_floating_point]
-        if not bufs:
+        flat = self._float_buffers()
+        if flat is None:
             return
-        flat = torch.cat([b.reshape(-1).float() for b in bufs])
         self.comm.all_reduce(flat)
         flat /= self.comm.world  # survivors only, after a failure
+        self._set_float_buffers(flat)
+
+    def _float_buffers(self):
+        """The model's float buffers (BN running stats) as one flat fp32 copy, or None."""
+        bufs = [b for b in self.model.buffers() if b.dtype.is_floating_point]
+        return torch.cat([b.reshape(-1).float() for b in bufs]) if bufs else None
+
+    @torch.no_grad()
+    def _set_float_buffers(self, flat: torch.Tensor) -> None:
         off = 0
-        with torch.no_grad():
-            for b in bufs:
+        for b in self.model.buffers():
+            if b.dtype.is_floating_point:
                 n = b.numel()
                 b.copy_(flat[off : off + n].view(b.shape).to(b.dtype))
                 off += n
-
-    def _wm_path(self, step: int | None = None) -> str:
-        # rank-local sidecar of the worker-momentum state.  The name must not match
-        # model_step_*, which evaluate.py globs and parses.
-        step = self.step_num if step is None else step
-        return os.path.join(self.cfg.train_dir, f"worker_momentum_step_{step}.rank{self.rank}")
 
     def save(self):
         self.sync_buffers()  # collective — every rank must call save() together
         if self.rank == 0:
             save_checkpoint(self._ckpt_path(), self.model, self.space, self.opt, self.step_num,
                             self.cfg, agg=self.agg)
-        if self._wm_beta > 0.0:
-            # the state is rank-local (P rows over all ranks), so every rank writes its
-            # own rows; per parameter, like the optimizer buffers (layout-independent)
-            from ..utils.checkpoint import _flat_to_params
-
-            path = self._wm_path()
-            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            state = {
-                "step": self.step_num,
-                "beta": self._wm_beta,
-                "world": self.world,
-                "L": self.L,
-                "first": list(self._wm_first),
-                "rows": [_flat_to_params(self.space, self._wm[l]) for l in range(self.L)],
-            }
-            tmp = path + ".tmp"
-            torch.save(state, tmp)
-            os.replace(tmp, path)
+        if self.wm is not None:
+            self.wm.save(WorkerMomentum.path(self.cfg.train_dir, self.step_num, self.rank),
+                         self.space, self.step_num, self.world)
 
     def load(self, step: int):
         load_checkpoint(self._ckpt_path(step), self.model, self.space, self.opt, agg=self.agg)
         self.step_num = step
-        if self._wm_beta > 0.0:
-            self._load_worker_momentum(step)
-
-    def _load_worker_momentum(self, step: int) -> None:
-        from ..utils.checkpoint import _params_to_flat
-
-        path = self._wm_path(step)
-        state = None
-        if os.path.exists(path):
-            state = torch.load(path, map_location="cpu", weights_only=False)
-            if state.get("world") != self.world or state.get("L") != self.L:
-                state = None  # rows of another worker layout are not this rank's workers
-        self._wm.zero_()
-        if state is None:
-            # every slot starts over with m = g on its next step
-            self._wm_first = [True] * self.L
-            self.logger.log({"step": step, "event": "worker_momentum_restart", "path": path})
-            return
-        for l in range(self.L):
-            _params_to_flat(self.space, state["rows"][l], self._wm[l])
-        self._wm_first = [bool(f) for f in state["first"]]
+        if self.wm is not None:
+            self.wm.load(WorkerMomentum.path(self.cfg.train_dir, step, self.rank),
+                         self.space, step, self.world, self.logger)
 
     def close(self):
         if self.health is not None:

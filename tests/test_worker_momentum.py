@@ -137,11 +137,11 @@ def test_trainer_sends_the_momentum_recurrence(tmp_path, monkeypatch):
     gradients the op was handed."""
     beta, steps, L = 0.9, 3, 4
     t0 = _spy_trainer(_lenet_cfg(tmp_path))
-    assert not hasattr(t0, "_wm")
+    assert t0.wm is None
     for _ in range(2):
         t0.train_step()
     t = _spy_trainer(_lenet_cfg(tmp_path, worker_momentum=beta), monkeypatch)
-    assert t._wm.shape == (L, t.space.d_pad) and t._wm_first == [True] * L
+    assert t.wm.state.shape == (L, t.space.d_pad) and t.wm.first == [True] * L
     prev = None
     for s in range(steps):
         t.train_step()
@@ -157,16 +157,16 @@ def test_trainer_sends_the_momentum_recurrence(tmp_path, monkeypatch):
             g_raw = raw[l][0]
             assert bool(torch.isfinite(g_raw).all()) and bool(g_raw.abs().max() > 0)
             if s == 0:
-                assert torch.equal(bits(t._wm[l]), bits(g_raw))
+                assert torch.equal(bits(t.wm.state[l]), bits(g_raw))
             else:
                 # the state is honest in EVERY slot, the Byzantine one included
-                check_update(g_raw, prev[l], t._wm[l], t._wm[l], beta, f"step {s} slot {l}")
+                check_update(g_raw, prev[l], t.wm.state[l], t.wm.state[l], beta, f"step {s} slot {l}")
             if l in byz:
-                assert torch.equal(bits(t.sent[s][l]), bits(t._wm[l] * fb.ADVERSARY_)), (s, l)
+                assert torch.equal(bits(t.sent[s][l]), bits(t.wm.state[l] * fb.ADVERSARY_)), (s, l)
             else:
-                assert torch.equal(bits(t.sent[s][l]), bits(t._wm[l])), (s, l)
-        prev = t._wm.clone()
-    assert t._wm_first == [False] * L
+                assert torch.equal(bits(t.sent[s][l]), bits(t.wm.state[l])), (s, l)
+        prev = t.wm.state.clone()
+    assert t.wm.first == [False] * L
     # what step 2 sends is the momenta, not the beta=0 run's gradients
     assert not torch.equal(t.sent[1], t0.sent[1])
     t.close()
@@ -177,7 +177,7 @@ def test_beta_zero_changes_nothing(tmp_path):
     out = []
     for kw in (dict(), dict(worker_momentum=0.0)):
         t = _spy_trainer(_lenet_cfg(tmp_path, momentum=0.5, **kw))
-        assert not hasattr(t, "_wm")
+        assert t.wm is None
         for _ in range(3):
             t.train_step()
         out.append(t.space.flat_param.clone())
@@ -205,8 +205,8 @@ def _bucket_worker(rank, world, mode, worker_fail):
             assert len(t._buckets) >= 2, "LeNet should split into several buckets"
         for s in range(3):
             t.train_step()
-            assert t._wm_first == [False, False]
-        out[bucket_mb] = (t.space.flat_param.clone(), t._wm.clone())
+            assert t.wm.first == [False, False]
+        out[bucket_mb] = (t.space.flat_param.clone(), t.wm.state.clone())
         t.close()
     for a, b in zip(out[0.0], out[0.01]):
         assert torch.equal(bits(a), bits(b)), float((a - b).abs().max())
@@ -230,7 +230,7 @@ def test_checkpoint_round_trip(tmp_path):
 
     t = trainer(eval_freq=2)
     losses = [t.train_step()["loss"] for _ in range(4)]  # saves after steps 2 and 4
-    ref_param, ref_wm = t.space.flat_param.clone(), t._wm.clone()
+    ref_param, ref_wm = t.space.flat_param.clone(), t.wm.state.clone()
     t.close()
     ckpt = str(tmp_path / "ckpt")
     side = os.path.join(ckpt, "worker_momentum_step_2.rank0")
@@ -244,11 +244,11 @@ def test_checkpoint_round_trip(tmp_path):
     assert state["first"] == [False] * 4 and len(state["rows"]) == 4
 
     t = trainer(checkpoint_step=2)
-    assert t._wm_first == [False] * 4
+    assert t.wm.first == [False] * 4
     resumed = [t.train_step()["loss"] for _ in range(2)]
     assert resumed == losses[2:]
     assert torch.equal(bits(t.space.flat_param), bits(ref_param))
-    assert torch.equal(bits(t._wm), bits(ref_wm))
+    assert torch.equal(bits(t.wm.state), bits(ref_wm))
     t.close()
 
     # sidecar of another worker layout, then no sidecar: every slot starts over
@@ -259,10 +259,10 @@ def test_checkpoint_round_trip(tmp_path):
         if remove:
             os.remove(side)
         t = trainer(checkpoint_step=2, log_dir=str(logs))
-        assert t._wm_first == [True] * 4 and not bool(t._wm.any())
+        assert t.wm.first == [True] * 4 and not bool(t.wm.state.any())
         again = [t.train_step()["loss"] for _ in range(2)]
         assert np.isfinite(again).all() and t.skipped_updates == 0
-        assert t._wm_first == [False] * 4
+        assert t.wm.first == [False] * 4
         t.close()
         with open(logs / "rank0.jsonl") as fh:
             events = [json.loads(line) for line in fh]

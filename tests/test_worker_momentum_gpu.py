@@ -164,16 +164,16 @@ def test_gpu_trainer_steps(tmp_path, hip_graphs):
                  worker_momentum=0.9, momentum=0.0, hip_graphs=hip_graphs)
     t = Trainer(cfg)
     t.logger.stdout_every = 0
-    assert t.use_graphs == hip_graphs and t.P == 4 and t._wm.shape == (4, t.space.d_pad)
+    assert t.use_graphs == hip_graphs and t.P == 4 and t.wm.state.shape == (4, t.space.d_pad)
     losses = [t.train_step()["loss"]]
-    wm1 = t._wm.clone()
+    wm1 = t.wm.state.clone()
     losses.append(t.train_step()["loss"])
     torch.cuda.synchronize()
     assert np.isfinite(losses).all()
     assert t.skipped_updates == 0
-    assert t._wm_first == [False] * 4
+    assert t.wm.first == [False] * 4
     for l in range(4):
-        assert bool(torch.isfinite(t._wm[l]).all()) and bool(wm1[l].abs().max() > 0)
-        assert bool(t._wm[l].abs().max() > 0)
-        assert not torch.equal(t._wm[l], wm1[l]), l
+        assert bool(torch.isfinite(t.wm.state[l]).all()) and bool(wm1[l].abs().max() > 0)
+        assert bool(t.wm.state[l].abs().max() > 0)
+        assert not torch.equal(t.wm.state[l], wm1[l]), l
     t.close()
