@@ -90,9 +90,34 @@ class Config:
                                   # logical worker sends m = beta*m + (1-beta)*g instead of g
                                   # (0 = off; baseline approach, colocated topology, with
                                   # --momentum 0 under sgd; see ops.worker_momentum_)
+    pre_aggregation: str = "none"  # none|nnm: nearest-neighbour mixing (arXiv:2302.01772) in
+                                   # front of the baseline rule: every exchanged row becomes
+                                   # the mean of its P-worker_fail nearest rows (baseline
+                                   # approach, colocated topology, 2*worker_fail < P <= 32;
+                                   # see parallel/mixing.py, ops.mix_rows_)
 
     def sanity(self):
         from .coding.collusion import COLLUDING_MODES
+
+        if self.pre_aggregation != "none":
+            what = f"pre-aggregation {self.pre_aggregation!r}: "
+            if self.pre_aggregation != "nnm":
+                raise ValueError(what + "--pre-aggregation must be none or nnm")
+            if self.approach != "baseline":
+                raise ValueError(
+                    what + "nearest-neighbour mixing needs --approach baseline (the coded "
+                    "approaches compare or decode the workers' gradients as they were sent), "
+                    f"got {self.approach!r}")
+            if self.topology == "ps":
+                raise ValueError(
+                    what + "nearest-neighbour mixing needs the colocated topology, not "
+                    "--topology ps")
+            if self.health_timeout > 0:
+                raise ValueError(
+                    what + "nearest-neighbour mixing cannot be combined with --health-timeout "
+                    "(the mixing of a survivor world is not built)")
+            if self.worker_fail < 1:
+                raise ValueError(what + "nearest-neighbour mixing needs --worker-fail >= 1")
 
         if self.worker_momentum != 0.0:
             what = f"worker-momentum {self.worker_momentum!r}: "

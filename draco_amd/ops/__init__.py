@@ -18,6 +18,7 @@ __all__ = [
     "collude_",
     "clip_step_",
     "worker_momentum_",
+    "mix_rows_",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -132,6 +133,21 @@ def worker_momentum_(g, m, beta, first):
         ext.worker_momentum(g, m, float(beta), bool(first))
         return
     fallback.worker_momentum_(g, m, beta, first)
+
+
+def mix_rows_(x, w, skip=()):
+    """In place on the exchanged (P, n) block, P <= 32: y[i, c] = sum over k not in `skip`
+    of w[i, k] * x[k, c], w a dense (P, P) fp32 tensor on x's device that is never read
+    on the host.  `skip` (a host sequence of distinct ints) reaches the kernel as a
+    64-bit mask by value; a skipped row is never loaded, so its NaNs reach no output, and
+    is still written.  On the GPU this is the one kernel on the matrix unit (fp32 MFMA,
+    W in registers, no second (P, n) buffer); two runs agree bit for bit.  Definition and
+    checks: fallback.mix_rows_."""
+    ext = _native_for(x)
+    if ext is not None:
+        ext.mix_rows(x, w, [int(r) for r in skip])
+        return
+    fallback.mix_rows_(x, w, skip)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

@@ -12,7 +12,8 @@
 // row selections), which sort each column in registers and are VALU-heavy.  k_collude
 // (colluding ALIE / inner-product adversaries) keeps a column in registers as they do,
 // four columns per lane, without the sort; k_clip_step (centered clipping) does the
-// same and carries per-row distance accumulators on top.
+// same and carries per-row distance accumulators on top.  k_mix_rows (nearest-neighbour
+// mixing, Y = W X in place) is the one kernel on the matrix unit (fp32 MFMA).
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -1450,6 +1451,118 @@ void worker_momentum(torch::Tensor g, torch::Tensor m, double beta, bool first) 
          (float4 *)gp, (float4 *)mp, n4, (float)beta, omb);
 }
 
+// --------------------------------------------------------------------------- row mixing
+// Y = W X in place on the (P, n) block, W a dense (P, P) fp32 matrix on device and rows
+// in `skip` left out of the sum: y[i, c] = sum over k not in skip of w[i, k] * x[k, c].
+// It is the heavy half of nearest-neighbour mixing (Allouah et al., "Fixing by Mixing",
+// arXiv:2302.01772: every row becomes the mean of its P-f nearest rows) and the one
+// kernel of this file on the matrix unit: at P = 32 a column costs 1024 FMAs for 256
+// bytes moved, and a one-column-per-lane vector kernel would fetch a W operand for every
+// one of them.  v_mfma_f32_32x32x2f32 keeps W, zero-padded to 32 x 32, in 16 registers
+// per lane for the whole kernel.  No LDS, no second (P, n) buffer.
+//
+// A wave owns MIX_COLS = 128 consecutive columns per trip.  Lane (h = lane / 32,
+// q = lane % 32) loads, for s = 0..15, the 16 bytes of row k = 2s + h at columns
+// 4q..4q+3 (a half-wave reads 512 contiguous bytes of one row).  The instruction takes
+// B[k = 2s + h][j = q] from lane (h, q): component t of those loads, across the lanes,
+// is the B operand of column tile t, whose 32 columns are 4j + t.  Which columns form a
+// tile is the kernel's choice, the instruction does not care.  A[i = q][k = 2s + h] =
+// w[i, k] comes from the same lane numbering.  4 tiles x 16 steps accumulate into four
+// 16-register tiles; register v of lane (h, q) holds row i = 8 (v / 4) + 4 h + v % 4 of
+// column j = q, so the four tiles' registers v are that row's columns 4q..4q+3 again:
+// one 16-byte store per (lane, v), 16 per lane, rows >= P not stored.
+//
+// Rows k >= P and rows in `skip` are never loaded; their B values AND their A values
+// are zero (0 * 0, never 0 * NaN), so neither a NaN in a skipped row of x nor whatever w
+// holds in that column reaches an output.  Steps whose two rows are both >= P are left
+// out (P is wave-uniform).  Every store of a lane depends, through the accumulators, on
+// every load of the wave's columns, and waves own disjoint columns, so in place is safe.
+// Fixed order, no atomics: two runs agree bit for bit.
+#define MIX_COLS 128
+// the kernel's only fp32 arithmetic is the matrix instruction; the packed VALU forms
+// (v_pk_add/mul/fma_f32) are switched off for it so that it stays that way
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NO_PACKED_FP32
+#endif
+typedef float acc16 __attribute__((ext_vector_type(16)));
+
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mix_rows(float *x, const float *__restrict__ w, int P, unsigned long long skip, long n) {
+  const int lane = threadIdx.x % WAVE, h = lane / 32, q = lane % 32;
+  float a[16];
+#pragma unroll
+  for (int s = 0; s < 16; ++s) {
+    int k = 2 * s + h;
+    a[s] = 0.f;
+    if (q < P && k < P && !((skip >> k) & 1ull)) a[s] = w[q * P + k];
+  }
+  long chunks = (n + MIX_COLS - 1) / MIX_COLS;
+  long c = blockIdx.x * (long)(NTHREADS / WAVE) + threadIdx.x / WAVE;
+  long cstride = gridDim.x * (long)(NTHREADS / WAVE);
+  for (; c < chunks; c += cstride) {  // wave-uniform trip count
+    long col = c * MIX_COLS + 4 * q;
+    bool in = col < n;  // n % 4 == 0: a float4 is inside or outside as a whole
+    // rows h and 4h of the lane's columns: the row loaded in step s and the row stored
+    // from register v lie a wave-uniform number of rows further on
+    const float *xl = x + h * n + col;
+    float *xs = x + 4 * h * n + col;
+    col4 b[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      int k = 2 * s + h;
+      b[s] = 0.f;
+      if (in && k < P && !((skip >> k) & 1ull))
+        b[s] = *reinterpret_cast<const col4 *>(xl + 2 * s * n);
+    }
+    acc16 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      if (2 * s < P) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s][t], acc[t], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      int i = 8 * (v / 4) + 4 * h + v % 4;
+      if (in && i < P) {
+        col4 y = {acc[0][v], acc[1][v], acc[2][v], acc[3][v]};
+        *reinterpret_cast<col4 *>(xs + (8 * (v / 4) + v % 4) * n) = y;
+      }
+    }
+  }
+}
+
+void mix_rows(torch::Tensor x, torch::Tensor w, std::vector<int64_t> skip) {
+  check_rows("mix_rows", x, true);
+  CHECK_IN(w);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 && w.scalar_type() == torch::kFloat32,
+              "mix_rows: x and w must be fp32");
+  long P = x.size(0), n = x.size(1);
+  TORCH_CHECK(P <= 32, "mix_rows kernel supports P <= 32 (one 32x32 matrix tile), got ", P);
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == P && w.size(1) == P, "mix_rows: w must have shape (",
+              P, ", ", P, ")");
+  TORCH_CHECK(w.device() == x.device(), "mix_rows: w must be on x's device");
+  unsigned long long mask = 0;
+  for (int64_t r : skip) {
+    TORCH_CHECK(0 <= r && r < P, "mix_rows: skip row ", r, " outside [0, ", P, ")");
+    unsigned long long bit = 1ull << r;
+    TORCH_CHECK(!(mask & bit), "mix_rows: skip row ", r, " listed twice");
+    mask |= bit;
+  }
+  if (P == 0 || n == 0) return;
+  float *xp = x.data_ptr<float>();
+  TORCH_CHECK((uintptr_t)xp % 16 == 0, "mix_rows: x must be 16-byte aligned");
+  long chunks = (n + MIX_COLS - 1) / MIX_COLS;
+  launch(k_mix_rows, dim3(n_blocks(chunks, NTHREADS / WAVE)), 0, xp, w.data_ptr<float>(), (int)P,
+         mask, n);
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -1479,4 +1592,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("collude", &collude);
   m.def("clip_step", &clip_step);
   m.def("worker_momentum", &worker_momentum);
+  m.def("mix_rows", &mix_rows);
 }

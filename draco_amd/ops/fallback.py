@@ -272,6 +272,52 @@ def worker_momentum_(g: torch.Tensor, m: torch.Tensor, beta: float, first: bool)
     g1.copy_(torch.where(fin, upd, g1))
 
 
+# --------------------------------------------------------------------- row mixing
+@torch.no_grad()
+def mix_rows_(x: torch.Tensor, w: torch.Tensor, skip=()) -> None:
+    """Y = W X in place on the (P, n) block with the rows in `skip` left out of the sum:
+    y[i, c] = sum over k not in skip of w[i, k] * x[k, c].  The heavy half of
+    nearest-neighbour mixing (arXiv:2302.01772; parallel/mixing.py builds W).
+
+    x: (P, n) fp32 contiguous, P <= 32, n % 4 == 0; w: (P, P) fp32 contiguous on x's
+    device, dense (not assumed 0/1 or symmetric), never read on the host; skip: distinct
+    ints in [0, P).  A skipped row is removed by selection, not multiplied by zero: its
+    NaN/Inf values reach no output, whatever w holds in its column.  It is still WRITTEN
+    like every other row.  With every row skipped the result is zero.  Other non-finite
+    values propagate by ordinary IEEE arithmetic (a NaN row of w gives a NaN row of y).
+    The HIP kernel sums in the matrix unit's order: it agrees within the rounding bound
+    2*(P+4)*2^-24 * sum_k |w[i,k] x[k,c]|, not bit for bit.
+    """
+    if x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError(f"mix_rows_: x and w must be fp32, got {x.dtype}, {w.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"mix_rows_: x must be 2D, got {x.dim()}D")
+    if not x.is_contiguous() or not w.is_contiguous():
+        raise ValueError("mix_rows_: x and w must be contiguous")
+    P, n = x.shape
+    if P > 32:
+        raise ValueError(f"mix_rows_ supports P <= 32, got {P}")
+    if n % 4 != 0:
+        raise ValueError(f"mix_rows_: row length must be a multiple of 4, got {n}")
+    if w.shape != (P, P):
+        raise ValueError(f"mix_rows_: w must have shape ({P}, {P}), got {tuple(w.shape)}")
+    if w.device != x.device:
+        raise ValueError("mix_rows_: w must be on x's device")
+    skip = [int(r) for r in skip]
+    for r in skip:
+        if not 0 <= r < P:
+            raise ValueError(f"mix_rows_: skip row {r} outside [0, {P})")
+    if len(set(skip)) != len(skip):
+        raise ValueError(f"mix_rows_: skip rows must be distinct, got {skip}")
+    if P == 0 or n == 0:
+        return
+    keep = [k for k in range(P) if k not in set(skip)]
+    if not keep:
+        x.zero_()
+        return
+    x.copy_(torch.mm(w[:, keep], x[keep]))
+
+
 # --------------------------------------------------------------------- vote
 @torch.no_grad()
 def rows_equal(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, atol: float) -> torch.Tensor:

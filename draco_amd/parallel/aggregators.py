@@ -63,6 +63,10 @@ class Aggregator:
     # honest rows only after the exchange, so they act inside exchanged().  The trainer
     # sets collusion.rows from the host-side schedule before every aggregate().
     collusion = None
+    # parallel.mixing.NearestNeighborMixing or None: a pre-aggregation step, applied to
+    # the exchanged block after the collusion overwrite (the adversary sees the honest
+    # raw rows, the rule sees the mixed rows)
+    mixing = None
     # the most rows the rule's HIP kernel holds (None: no limit) and why; _check_rows
     # is the CPU-side config check, so a bad count fails at construction and not at
     # the first kernel launch on the GPU
@@ -142,12 +146,15 @@ class Aggregator:
     def exchanged(self, payload: torch.Tensor) -> torch.Tensor:
         """(rows, d_pad) payload -> (rows*world, shard) in l-major row order.  With a
         collusion attached, the step's Byzantine rows of that block are overwritten
-        (ops.collude_) before the rule reads it."""
+        (ops.collude_) before the rule reads it; with a mixing attached, the block is
+        then mixed in place."""
         recv = self._exchange(payload)
         col = self.collusion
         if col is not None and col.rows:
             # baseline approach: recv row l*world + src IS logical worker l*world + src
             ops.collude_(recv, col.rows, col.a, col.b)
+        if self.mixing is not None:
+            self.mixing(recv)
         return recv
 
     def _check_rows(self, P: int) -> None:
@@ -970,12 +977,18 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
         raise ValueError(f"baseline approach supports modes {BASELINE_MODES}, got {cfg.mode!r}")
     cls, args = _BASELINE_RULES[cfg.mode]
     kwargs, name, hint = args(cfg), None, ""
-    if cfg.mode == "normal" and cfg.err_mode in COLLUDING_MODES:
+    nnm = cfg.pre_aggregation == "nnm"
+    if cfg.pre_aggregation not in ("none", "nnm"):
+        raise ValueError(f"pre-aggregation must be none or nnm, got {cfg.pre_aggregation!r}")
+    if cfg.mode == "normal" and (cfg.err_mode in COLLUDING_MODES or nnm):
         # MeanAggregator sums inside the reduce-scatter: the honest rows are never
-        # visible together.  Under a colluding adversary the plain mean goes over
-        # the exchange path instead: the trimmed mean with nothing trimmed.
+        # visible together.  Under a colluding adversary, and behind a pre-aggregation,
+        # the plain mean goes over the exchange path instead: the trimmed mean with
+        # nothing trimmed.
         cls, kwargs, name = TrimmedMeanAggregator, {"trim": 0}, "mean"
-        hint = (f" (mode 'normal' under the colluding err mode {cfg.err_mode!r} is the "
+        why = (f"the colluding err mode {cfg.err_mode!r}" if cfg.err_mode in COLLUDING_MODES
+               else "--pre-aggregation nnm")
+        hint = (f" (mode 'normal' under {why} is the "
                 "trim=0 mean over the exchange path, so that kernel's limit of 64 workers "
                 "applies)")
     elif cfg.mode in ("multi_krum", "bulyan"):
@@ -988,4 +1001,8 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
         raise ValueError(f"{e}{hint}") from None
     if name is not None:
         agg.name = name
+    if nnm:
+        from .mixing import NearestNeighborMixing  # mixing imports this module
+
+        agg.mixing = NearestNeighborMixing(comm, cfg.worker_fail, num_workers)
     return agg

@@ -426,6 +426,50 @@ def worker_momentum_compare(rounds=3, beta=0.9):
         print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def mix_rows_compare(rounds=3):
+    """mix_rows_ (nearest-neighbour mixing: Y = W X in place on the matrix unit) at
+    24 x 11.2M and 32 x 11.2M with one row skipped, against the route a user would
+    otherwise write on the same tensors: torch.mm(W, x, out=second_buffer) (rocBLAS; it
+    needs the second (P, n) buffer and cannot skip a row).  Both move 2*P*n*4 bytes, the
+    streaming floor GB/s is counted against.  The kernel's result is checked against
+    fp64 on a column sample first (W is the NNM shape, P-1 equal weights per row; x is
+    mixed again and again by the timed calls and stays bounded, rows of W sum to 1); the
+    arms alternate inside each round; min-max over the rounds per arm."""
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    for rows in (24, 32):
+        gen = torch.Generator().manual_seed(rows)
+        near = torch.stack([torch.randperm(rows, generator=gen)[: rows - 1] for _ in range(rows)])
+        w = torch.zeros(rows, rows).scatter_(1, near, 1.0 / (rows - 1))
+        skip = [rows - 1]
+        w[:, skip] = 0.0
+        w = w.to(DEV)
+        x = torch.randn(rows, d, device=DEV)
+        second = torch.empty_like(x)
+        x0 = x[:, :65536].double()
+        ops.mix_rows_(x, w, skip)
+        ref = w.double() @ x0
+        tol = 2 * (rows + 4) * 2.0 ** -24 * (w.double().abs() @ x0.abs())
+        assert bool(((x[:, :65536].double() - ref).abs() <= tol).all()), rows
+        blk = 2 * 4 * rows * d
+        arms = [
+            (f"mix_rows_ ({rows} rows, 1 skipped)", lambda: ops.mix_rows_(x, w, skip)),
+            (f"torch.mm(W, x, out=) ({rows} rows)", lambda: torch.mm(w, x, out=second)),
+        ]
+        times = {name: [] for name, _ in arms}
+        for r in range(rounds):
+            print(f"# round {r}")
+            for name, fn in arms:
+                ms = t_ms(fn, iters=100, warmup=10)
+                times[name].append(ms)
+                report(name, ms, blk)
+        print("# min - max over rounds")
+        for name, _ in arms:
+            lo, hi = min(times[name]), max(times[name])
+            print(f"{name:34} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+        del x, second
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -555,6 +599,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("WORKER_MOMENTUM_ONLY") == "1":
         worker_momentum_compare()
+        raise SystemExit(0)
+    if os.environ.get("NNM_ONLY") == "1":
+        mix_rows_compare()
         raise SystemExit(0)
     if os.environ.get("BULYAN_ONLY") == "1":
         bulyan_compare()
