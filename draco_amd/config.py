@@ -39,8 +39,13 @@ class Config:
     adversarial: int = 1              # parity flag (err magnitude switch; reference hardcodes -100)
     worker_fail: int = 2
     group_size: int = 5
-    compress_grad: str = "none"       # none|bf16 wire dtype for gradient exchange (replaces the
-                                      # reference's blosc/snappy CPU compression)
+    compress_grad: str = "none"       # none|bf16|sign wire format of the gradient exchange (bf16
+                                      # replaces the reference's blosc/snappy CPU compression,
+                                      # SURVEY §2.2 K12, for maj_vote / cyclic; sign is signSGD
+                                      # with majority vote, arXiv:1810.05291: 2 bits per element,
+                                      # baseline approach, mode normal, colocated topology, at
+                                      # most 64 workers; the step is lr per coordinate; see
+                                      # parallel/aggregators.SignMajorityAggregator)
     checkpoint_step: int = 0
     optimizer: str = "sgd"            # sgd|adam (fused flat kernels, optim/flat_sgd.py)
 
@@ -98,6 +103,28 @@ class Config:
 
     def sanity(self):
         from .coding.collusion import COLLUDING_MODES
+
+        if self.compress_grad == "sign":
+            what = ("compress-grad 'sign' (signSGD with majority vote, the sign wire of the "
+                    "plain mean): ")
+            if self.approach != "baseline" or self.mode != "normal":
+                raise ValueError(
+                    what + "needs --approach baseline --mode normal, got approach "
+                    f"{self.approach!r}, mode {self.mode!r}")
+            if self.topology == "ps":
+                raise ValueError(what + "needs the colocated topology, not --topology ps")
+            if self.health_timeout > 0:
+                raise ValueError(
+                    what + "cannot be combined with --health-timeout (the packed exchange "
+                    "of a survivor world is not built)")
+            if self.err_mode in COLLUDING_MODES:
+                raise ValueError(
+                    what + f"cannot be combined with the colluding err mode {self.err_mode!r} "
+                    "(it acts on an fp32 exchanged block; the rows travel as sign bits)")
+            if self.pre_aggregation != "none":
+                raise ValueError(
+                    what + "cannot be combined with --pre-aggregation "
+                    f"{self.pre_aggregation} (it mixes an fp32 exchanged block)")
 
         if self.pre_aggregation != "none":
             what = f"pre-aggregation {self.pre_aggregation!r}: "
@@ -163,6 +190,13 @@ class Config:
             raise ValueError("cyclic approach needs worker-fail >= 1")
 
 
+_HELP = {
+    "compress_grad": "none | bf16 (alias compress: bf16 wire for maj_vote / cyclic) | sign "
+                     "(signSGD with majority vote: 2-bit sign wire, --approach baseline --mode "
+                     "normal)",
+}
+
+
 def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     for f in fields(Config):
         flag = "--" + f.name.replace("_", "-")
@@ -170,7 +204,8 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
             parser.add_argument(flag, type=lambda s: s.lower() in ("1", "true", "yes"),
                                 default=f.default)
         else:
-            parser.add_argument(flag, type=type(f.default), default=f.default)
+            parser.add_argument(flag, type=type(f.default), default=f.default,
+                                help=_HELP.get(f.name))
     # accepted-for-parity flags with no framework meaning
     parser.add_argument("--hostfile", type=str, default="", help="accepted for CLI parity; ranks come from torchrun env")
     parser.add_argument("--no-cuda", action="store_true", default=False)

@@ -19,6 +19,8 @@ __all__ = [
     "clip_step_",
     "worker_momentum_",
     "mix_rows_",
+    "sign_pack",
+    "sign_majority",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -148,6 +150,32 @@ def mix_rows_(x, w, skip=()):
         ext.mix_rows(x, w, [int(r) for r in skip])
         return
     fallback.mix_rows_(x, w, skip)
+
+
+def sign_pack(g, out):
+    """The signSGD wire format: out (n/16,) int32 = the votes of g (n,) fp32, n % 64 == 0,
+    two bits per element (+1: g > 0, -1: g < 0, abstain: +-0 and NaN), 16 bytes per 64
+    elements; a 64-aligned slice of g packs to the matching slice of out.  The kernel
+    (wave ballots) and the fallback write the same bytes.  Layout and checks:
+    fallback.sign_pack."""
+    ext = _native_for(g)
+    if ext is not None:
+        ext.sign_pack(g, out)
+        return
+    fallback.sign_pack(g, out)
+
+
+def sign_majority(packed, out):
+    """out (n,) fp32 = sign(#pos - #neg) per coordinate over the P <= 64 rows of packed
+    (P, n/16) int32 in sign_pack's format: +1.0, -1.0 or +0.0, always finite.  On the GPU
+    a bit-sliced vote (vertical counters, 64 coordinates per lane at once) in a fixed
+    order: two runs agree bit for bit, and with the fallback.  Definition and checks:
+    fallback.sign_majority."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.sign_majority(packed, out)
+        return
+    fallback.sign_majority(packed, out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

@@ -14,6 +14,8 @@
 // four columns per lane, without the sort; k_clip_step (centered clipping) does the
 // same and carries per-row distance accumulators on top.  k_mix_rows (nearest-neighbour
 // mixing, Y = W X in place) is the one kernel on the matrix unit (fp32 MFMA).
+// k_sign_pack / k_sign_majority (signSGD with majority vote) are the bit kernels: wave
+// ballots pack two sign bits per element, bit-sliced counters vote on 64 elements at once.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -1563,6 +1565,216 @@ void mix_rows(torch::Tensor x, torch::Tensor w, std::vector<int64_t> skip) {
          mask, n);
 }
 
+// --------------------------------------------------------------------------- sign majority
+// signSGD with majority vote (Bernstein et al., arXiv:1810.05291): a worker sends the sign
+// of every gradient coordinate, the server takes the per-coordinate majority.  The vote of
+// a value g is +1 (g > 0), -1 (g < 0) or 0 (abstain: +0.0, -0.0, NaN); +-Inf and
+// subnormals vote their sign.  It is read off the bit pattern, never a float compare (no
+// flush of subnormals) and never the raw sign bit (-0.0 and NaN abstain).
+//
+// PACKED FORMAT (the one description; fallback.sign_pack produces the same bytes).  Two
+// bits per element, a `neg` plane and a `pos` plane.  Elements [64 r, 64 r + 64) form
+// record r: four int32 words, 16 bytes, at words 4r .. 4r+3 of the packed row,
+//     word 0 = neg bits 0..31, word 1 = neg bits 32..63,
+//     word 2 = pos bits 0..31, word 3 = pos bits 32..63,
+// and element e = 4 l + c of the record (l = 0..15, c = 0..3) is bit 16 c + l of its
+// plane.  The bit of an element depends on its index alone, and records are whole and in
+// order, so the packing of a 64-aligned slice of a row is the matching slice of the packed
+// row: the even all_to_all split of a packed row lands every rank's shard (a multiple of
+// 64 elements) on it.  The 16 c + l order is what four wave ballots over a float4 per lane
+// give without a transpose: bits 16 k .. 16 k + 15 of ballot c are lanes 16 k .. 16 k + 15,
+// the 16 float4s of the wave's k-th record.  A row with both bits of an element set (no
+// sign_pack output has one) counts once for each side: it cancels itself and abstains.
+//
+// k_sign_pack: one streaming pass, 4 B read and 0.25 B written per element, no LDS, no
+// atomics.  A wave owns SIGN_TRIP chunks of 256 consecutive elements per trip; all its
+// float4 loads are issued first, then per chunk eight ballots (neg, pos for c = 0..3)
+// executed by every lane, and lanes 0..3 assemble and store the chunk's four records, one
+// 16-byte store each (64 contiguous bytes).  n % 64 == 0: a lane's float4 and a record are
+// inside or outside as a whole; an outside lane votes 0 and an outside record is not
+// stored, which is all that n % 256 in {64, 128, 192} needs.
+#define SIGN_TRIP 4
+
+__device__ __forceinline__ void sign_votes(unsigned u, bool &neg, bool &pos) {
+  unsigned a = u & 0x7fffffffu;
+  bool votes = a != 0u && a <= 0x7f800000u;  // not +-0, not NaN
+  neg = votes && (u >> 31);
+  pos = votes && !(u >> 31);
+}
+
+// integer work only; the packed fp32 VALU forms stay off as for k_mix_rows
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_sign_pack(const uint4 *__restrict__ g, int4 *__restrict__ out, long n) {
+  const int lane = threadIdx.x % WAVE;
+  long chunks = (n + 255) / 256, nrec = n / 64;
+  long c = (blockIdx.x * (long)(NTHREADS / WAVE) + threadIdx.x / WAVE) * SIGN_TRIP;
+  long cstride = gridDim.x * (long)(NTHREADS / WAVE) * SIGN_TRIP;
+  for (; c < chunks; c += cstride) {  // wave-uniform trip count: every lane ballots
+    uint4 v[SIGN_TRIP];
+#pragma unroll
+    for (int j = 0; j < SIGN_TRIP; ++j) {
+      long i4 = (c + j) * 64 + lane;  // the lane's float4
+      v[j] = make_uint4(0u, 0u, 0u, 0u);
+      if (i4 * 4 < n) v[j] = g[i4];
+    }
+#pragma unroll
+    for (int j = 0; j < SIGN_TRIP; ++j) {
+      unsigned u[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+      unsigned long long bn[4], bp[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        bool neg, pos;
+        sign_votes(u[k], neg, pos);
+        bn[k] = __builtin_amdgcn_ballot_w64(neg);
+        bp[k] = __builtin_amdgcn_ballot_w64(pos);
+      }
+      // lane k < 4: record k of the chunk is bits 16k .. 16k+15 of the eight ballots
+      int sh = 16 * (lane & 3);
+      unsigned w[4];
+      w[0] = (unsigned)((bn[0] >> sh) & 0xffffu) | (unsigned)((bn[1] >> sh) & 0xffffu) << 16;
+      w[1] = (unsigned)((bn[2] >> sh) & 0xffffu) | (unsigned)((bn[3] >> sh) & 0xffffu) << 16;
+      w[2] = (unsigned)((bp[0] >> sh) & 0xffffu) | (unsigned)((bp[1] >> sh) & 0xffffu) << 16;
+      w[3] = (unsigned)((bp[2] >> sh) & 0xffffu) | (unsigned)((bp[3] >> sh) & 0xffffu) << 16;
+      long rec = (c + j) * 4 + lane;
+      if (lane < 4 && rec < nrec) out[rec] = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
+    }
+  }
+}
+
+// the checks shared by sign_pack and sign_majority: values (n,) fp32 and rows of n/16 int32
+static inline void check_sign(const char *op, const torch::Tensor &vals, const torch::Tensor &bits,
+                              long n) {
+  CHECK_IN(vals);
+  CHECK_IN(bits);
+  TORCH_CHECK(vals.device() == bits.device(), op, ": tensors must be on one device");
+  TORCH_CHECK(vals.scalar_type() == torch::kFloat32, op, ": values must be fp32");
+  TORCH_CHECK(bits.scalar_type() == torch::kInt32, op, ": packed signs must be int32");
+  TORCH_CHECK(vals.dim() == 1 && vals.numel() == n, op, ": values must be 1D of length ", n);
+  TORCH_CHECK(n % 64 == 0, op, ": length must be a multiple of 64, got ", n);
+}
+
+void sign_pack(torch::Tensor g, torch::Tensor out) {
+  long n = g.numel();
+  check_sign("sign_pack", g, out, n);
+  TORCH_CHECK(out.dim() == 1 && out.numel() == n / 16, "sign_pack: out must be 1D of length ",
+              n / 16, ", got ", out.numel());
+  if (n == 0) return;
+  const float *gp = g.data_ptr<float>();
+  int *op = out.data_ptr<int>();
+  TORCH_CHECK((uintptr_t)gp % 16 == 0 && (uintptr_t)op % 16 == 0,
+              "sign_pack: g and out must be 16-byte aligned");
+  long chunks = (n + 255) / 256;
+  int blocks = n_blocks((chunks + SIGN_TRIP - 1) / SIGN_TRIP, NTHREADS / WAVE);
+  launch(k_sign_pack, dim3(blocks), 0, (const uint4 *)gp, (int4 *)op, n);
+}
+
+// k_sign_majority: out[j] = sign(#pos_j - #neg_j) over the P packed rows, in {-1, +0, +1},
+// bit-sliced.  A lane owns one record (64 elements) per trip, a block 256 consecutive ones.
+// Per row the lane reads its record with one 16-byte load (a wave reads 1 KB contiguous;
+// four rows in flight) and adds the two 64-bit planes into two vertical counters of NB
+// bit-planes each (NB = bits of P, at most 7: counts reach 64) with a ripple add: per plane
+// an AND for the carry and an XOR, 64 elements at once.  A bit-sliced compare from the top
+// plane down then gives the masks pos > neg and neg > pos.
+//
+// The store is coalesced through LDS: every lane parks its two masks (16 B), and in step
+// s = 0..15 lane L fetches the masks of its wave's record 4 s + L / 16 (one 16-byte LDS
+// read, four distinct addresses per wave) and writes that record's elements
+// 4 (L % 16) .. + 3 as one float4, so a wave stores 1 KB of consecutive floats per step.  The
+// trip count is uniform over the block (the two __syncthreads()).  Fixed order, no
+// atomics: two runs agree bit for bit.  Ties, all-abstain columns and the zero pad tail
+// give +0.0; the result is always finite.
+template <int NB>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_sign_majority(const int4 *__restrict__ packed, float4 *__restrict__ out, int P, long R) {
+  typedef unsigned long long u64;
+  __shared__ ulonglong2 s_mask[NTHREADS];
+  const int tid = threadIdx.x, lane = tid % WAVE, wave0 = tid - lane;
+  for (long base = blockIdx.x * (long)NTHREADS; base < R; base += gridDim.x * (long)NTHREADS) {
+    long r = base + tid;
+    bool in = r < R;
+    u64 cn[NB], cp[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) cn[k] = cp[k] = 0ull;
+    for (int p0 = 0; p0 < P; p0 += 4) {
+      int4 w[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        w[j] = make_int4(0, 0, 0, 0);
+        if (in && p0 + j < P) w[j] = packed[(long)(p0 + j) * R + r];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        u64 carry_n = (u64)(unsigned)w[j].x | (u64)(unsigned)w[j].y << 32;
+        u64 carry_p = (u64)(unsigned)w[j].z | (u64)(unsigned)w[j].w << 32;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+          u64 tn = cn[k] & carry_n, tp = cp[k] & carry_p;
+          cn[k] ^= carry_n;
+          cp[k] ^= carry_p;
+          carry_n = tn;
+          carry_p = tp;
+        }
+      }
+    }
+    u64 gt = 0ull, lt = 0ull, eq = ~0ull;
+#pragma unroll
+    for (int k = NB - 1; k >= 0; --k) {
+      gt |= eq & cp[k] & ~cn[k];
+      lt |= eq & cn[k] & ~cp[k];
+      eq &= ~(cp[k] ^ cn[k]);
+    }
+    s_mask[tid] = make_ulonglong2(gt, lt);
+    __syncthreads();
+    const int l = lane % 16;
+#pragma unroll 4
+    for (int s = 0; s < 16; ++s) {
+      int src = 4 * s + lane / 16;
+      long rec = base + wave0 + src;
+      ulonglong2 m = s_mask[wave0 + src];
+      unsigned f[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        unsigned g1 = (unsigned)(m.x >> (16 * c + l)) & 1u;
+        unsigned l1 = (unsigned)(m.y >> (16 * c + l)) & 1u;
+        f[c] = (g1 | l1) * 0x3f800000u | l1 << 31;  // gt and lt are disjoint
+      }
+      if (rec < R)
+        out[rec * 16 + l] = make_float4(__uint_as_float(f[0]), __uint_as_float(f[1]),
+                                        __uint_as_float(f[2]), __uint_as_float(f[3]));
+    }
+    __syncthreads();  // the next trip overwrites s_mask
+  }
+}
+
+void sign_majority(torch::Tensor packed, torch::Tensor out) {
+  long n = out.numel();
+  check_sign("sign_majority", out, packed, n);
+  TORCH_CHECK(packed.dim() == 2 && packed.size(1) == n / 16,
+              "sign_majority: packed must be (P, ", n / 16, "), one row of n/16 words per worker");
+  long P = packed.size(0), R = n / 64;
+  TORCH_CHECK(P <= 64, "sign_majority kernel supports P <= 64 (7 counter planes), got ", P);
+  if (n == 0 || P == 0) return;  // no launch; with no rows out is left as it is
+  const int *pp = packed.data_ptr<int>();
+  float *op = out.data_ptr<float>();
+  TORCH_CHECK((uintptr_t)pp % 16 == 0 && (uintptr_t)op % 16 == 0,
+              "sign_majority: packed and out must be 16-byte aligned");
+  int nb = 1;
+  while ((1L << nb) <= P) ++nb;  // counts 0..P need nb = bits of P planes
+  auto run = [&](auto planes) {
+    launch(k_sign_majority<decltype(planes)::value>, dim3(n_blocks(R, NTHREADS)), 0,
+           (const int4 *)pp, (float4 *)op, (int)P, R);
+  };
+  switch (nb) {
+    case 1: run(std::integral_constant<int, 1>{}); break;
+    case 2: run(std::integral_constant<int, 2>{}); break;
+    case 3: run(std::integral_constant<int, 3>{}); break;
+    case 4: run(std::integral_constant<int, 4>{}); break;
+    case 5: run(std::integral_constant<int, 5>{}); break;
+    case 6: run(std::integral_constant<int, 6>{}); break;
+    default: run(std::integral_constant<int, 7>{}); break;
+  }
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -1593,4 +1805,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("clip_step", &clip_step);
   m.def("worker_momentum", &worker_momentum);
   m.def("mix_rows", &mix_rows);
+  m.def("sign_pack", &sign_pack);
+  m.def("sign_majority", &sign_majority);
 }

@@ -318,6 +318,79 @@ def mix_rows_(x: torch.Tensor, w: torch.Tensor, skip=()) -> None:
     x.copy_(torch.mm(w[:, keep], x[keep]))
 
 
+# --------------------------------------------------------------------- sign majority
+def _check_sign(op: str, vals: torch.Tensor, bits: torch.Tensor, n: int) -> None:
+    if vals.dtype != torch.float32:
+        raise ValueError(f"{op}: values must be fp32, got {vals.dtype}")
+    if bits.dtype != torch.int32:
+        raise ValueError(f"{op}: packed signs must be int32, got {bits.dtype}")
+    if not vals.is_contiguous() or not bits.is_contiguous():
+        raise ValueError(f"{op}: tensors must be contiguous")
+    if vals.device != bits.device:
+        raise ValueError(f"{op}: tensors must be on one device")
+    if vals.dim() != 1 or n % 64 != 0:
+        raise ValueError(f"{op}: values must be 1D with a length that is a multiple of 64, "
+                         f"got shape {tuple(vals.shape)}")
+
+
+@torch.no_grad()
+def sign_pack(g: torch.Tensor, out: torch.Tensor) -> None:
+    """The signSGD wire format (arXiv:1810.05291): out = the votes of g, two bits each.
+
+    g: (n,) fp32 contiguous, n % 64 == 0; out: (n/16,) int32 on g's device.  The vote of a
+    value is +1 (g > 0), -1 (g < 0) or 0 (+0.0, -0.0 and NaN abstain); +-Inf and
+    subnormals vote their sign.  It is read off the bit pattern, so no float compare can
+    flush a subnormal.  Elements [64r, 64r + 64) form record r = words 4r..4r+3:
+    (neg bits 0..31, neg bits 32..63, pos bits 0..31, pos bits 32..63), element 4l + c of
+    the record (l < 16, c < 4) at bit 16c + l of its plane: the layout documented above
+    k_sign_pack in draco_kernels.hip, which writes the same bytes.  A 64-aligned slice of
+    g packs to the matching slice of out.
+    """
+    n = g.numel()
+    _check_sign("sign_pack", g, out, n)
+    if out.dim() != 1 or out.numel() != n // 16:
+        raise ValueError(f"sign_pack: out must be 1D of length {n // 16}, got "
+                         f"{tuple(out.shape)}")
+    if n == 0:
+        return
+    u = g.view(torch.int32)
+    a = u & 0x7FFFFFFF
+    votes = (a != 0) & (a <= 0x7F800000)
+    planes = torch.stack([votes & (u < 0), votes & (u >= 0)])  # (neg, pos) x (n,)
+    # (plane, R, l, c) -> (R, plane, c, l): bit 16c + l, 32 bits per word
+    bits = planes.view(2, -1, 16, 4).permute(1, 0, 3, 2).reshape(-1, 32).to(torch.int64)
+    words = (bits << torch.arange(32, device=g.device)).sum(dim=1)
+    out.copy_(torch.where(words >= 2 ** 31, words - 2 ** 32, words))
+
+
+@torch.no_grad()
+def sign_majority(packed: torch.Tensor, out: torch.Tensor) -> None:
+    """out[j] = sign(#pos_j - #neg_j) over the P packed rows: +1.0, -1.0 or +0.0 (ties,
+    all-abstain columns and the zero pad tail), always finite.
+
+    packed: (P, n/16) int32 contiguous, rows in sign_pack's format, P <= 64; out: (n,)
+    fp32 on its device, n % 64 == 0.  A row counts at most once per coordinate whatever
+    its bits are: one with both bits of an element set adds one to each side and so
+    abstains.  n == 0 or P == 0 returns at once (with P == 0, out is left as it is).
+    """
+    n = out.numel()
+    _check_sign("sign_majority", out, packed, n)
+    if packed.dim() != 2 or packed.shape[1] != n // 16:
+        raise ValueError(f"sign_majority: packed must be (P, {n // 16}), got "
+                         f"{tuple(packed.shape)}")
+    P = packed.shape[0]
+    if P > 64:
+        raise ValueError(f"sign_majority supports P <= 64, got {P}")
+    if n == 0 or P == 0:
+        return
+    shifts = torch.arange(32, device=packed.device, dtype=torch.int32)
+    bits = (packed.view(P, -1, 2, 2, 1) >> shifts) & 1  # (P, R, plane, word, bit)
+    # bit 16c + l of a plane -> element 4l + c of the record
+    count = bits.view(P, -1, 2, 4, 16).sum(dim=0, dtype=torch.int32)  # (R, plane, c, l)
+    diff = (count[:, 1] - count[:, 0]).transpose(1, 2).reshape(-1)  # (R, l, c) -> (n,)
+    out.copy_(torch.sign(diff))
+
+
 # --------------------------------------------------------------------- vote
 @torch.no_grad()
 def rows_equal(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, atol: float) -> torch.Tensor:

@@ -17,6 +17,7 @@ all_gather of the decoded shard.  Reference semantics per policy:
   meamed       (not in the reference) arXiv:1802.10116  (mean of the P-b values nearest the median)
   phocas       (not in the reference) arXiv:1805.09682  (mean of the P-b values nearest the b-trimmed mean)
   centered_clip (not in the reference) arXiv:2012.10333 (iterated clipped steps from the previous aggregate)
+  sign_majority (not in the reference) arXiv:1810.05291 (signSGD: 2-bit sign wire, majority vote)
   cyclic       cyclic_master.py:103-188             (DFT-code algebraic decode)
 """
 from __future__ import annotations
@@ -876,6 +877,78 @@ class CenteredClipAggregator(Aggregator):
         return self._out
 
 
+class SignMajorityAggregator(Aggregator):
+    """signSGD with majority vote (Bernstein et al., arXiv:1810.05291), sharded over d: a
+    wire format of the plain mean.  Every worker sends the SIGN of each coordinate, two
+    bits per element (ops.sign_pack: 16x fewer all_to_all bytes than fp32 rows); the
+    aggregate is the per-coordinate majority sign(#pos - #neg) in {-1.0, +0.0, +1.0}
+    (ops.sign_majority), so the server's step is lr per coordinate.  With
+    --worker-momentum the signed row is the worker's momentum: the paper's Signum.
+
+    Shape: start_row packs the payload row into a persistent (rows, d_pad/16) int32 send
+    buffer and posts its all_to_all (the bf16 send path's pattern: it overlaps the next
+    worker's backward); aggregate exchanges the rest, votes on the (P, shard/16) block of
+    the local shard with ONE kernel, and all_gathers the fp32 result (P times smaller
+    than the exchange; a packed gather is not built).  Shards are multiples of 64
+    elements, so the even split of a packed row lands each rank's shard on it.  With one
+    rank the rows are still packed and voted.  P is taken per call.
+
+    The bucketed path is not built for this rule: start_bucket and mark_row_started do
+    nothing and the row ships whole from aggregate().  The rule never runs exchanged():
+    colluding adversaries and pre-aggregations, which act on an fp32 exchanged block, are
+    rejected by Config and the builder.
+
+    Guarantee and its limits.  A worker has exactly one vote per coordinate whatever it
+    sends, NaN, Inf and crafted bits included (+-0 and NaN abstain; a row with both bits
+    of a coordinate set cancels itself), and the output is always finite.  f Byzantine
+    workers flip a coordinate only where the honest margin |#pos - #neg| is at most f;
+    where the honest workers themselves are split, that is often.  Magnitudes are gone:
+    lr is the step per coordinate and has to be chosen for that.
+    """
+
+    name = "sign_majority"
+    MAX_WORKERS = 64
+    MAX_WORKERS_WHY = "the sign-majority HIP kernel counts votes in 7 bit-planes"
+
+    def __init__(self, comm, space, num_workers: int):
+        super().__init__(comm, space)
+        self.num_workers = num_workers
+        self._check_rows(num_workers)
+        self._send_bits = None  # (rows, d_pad/16) int32
+        self._recv_bits = None  # (rows, world, shard/16) int32; the send buffer at world 1
+
+    def start_row(self, payload: torch.Tensor, row: int) -> None:
+        rows = payload.shape[0]
+        if self._send_bits is None or self._send_bits.shape[0] != rows:
+            self._send_bits = torch.empty(rows, self.space.d_pad // 16, dtype=torch.int32,
+                                          device=payload.device)
+            self._recv_bits = (torch.empty(rows, self.comm.world, self.space.shard // 16,
+                                           dtype=torch.int32, device=payload.device)
+                               if self.comm.distributed else self._send_bits)
+        ops.sign_pack(payload[row], self._send_bits[row])
+        if self.comm.distributed:
+            w = self.comm.all_to_all_row(self._send_bits[row], self._recv_bits[row],
+                                         async_op=True)
+            if w is not None:
+                self._works.append(w)
+        self._started.add(row)
+
+    def start_bucket(self, payload: torch.Tensor, row: int, lo: int, hi: int) -> None:
+        pass
+
+    def mark_row_started(self, row: int) -> None:
+        pass
+
+    def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
+        self._start_rest(payload)
+        self._drain()
+        block = self._recv_bits.view(-1, self.space.shard // 16)  # (P, shard/16), l-major
+        self._check_rows(block.shape[0])
+        ops.sign_majority(block, self._shard_out)
+        self.comm.all_gather_shard(self._shard_out, self._out)
+        return self._out
+
+
 class CyclicAggregator(Aggregator):
     """Cyclic-code algebraic decode, sharded over d.
 
@@ -980,6 +1053,16 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
     nnm = cfg.pre_aggregation == "nnm"
     if cfg.pre_aggregation not in ("none", "nnm"):
         raise ValueError(f"pre-aggregation must be none or nnm, got {cfg.pre_aggregation!r}")
+    if cfg.compress_grad == "sign":
+        # signSGD with majority vote: a wire format of the plain mean.  The rows travel
+        # as sign bits, so nothing that reads or rewrites an fp32 exchanged block applies.
+        if cfg.mode != "normal" or cfg.err_mode in COLLUDING_MODES or nnm:
+            raise ValueError(
+                "compress-grad 'sign' is the sign wire of mode 'normal' alone, without a "
+                f"colluding err mode ({'/'.join(COLLUDING_MODES)}) or --pre-aggregation nnm; "
+                f"got mode {cfg.mode!r}, err mode {cfg.err_mode!r}, pre-aggregation "
+                f"{cfg.pre_aggregation!r}")
+        return SignMajorityAggregator(comm, space, num_workers=num_workers)
     if cfg.mode == "normal" and (cfg.err_mode in COLLUDING_MODES or nnm):
         # MeanAggregator sums inside the reduce-scatter: the honest rows are never
         # visible together.  Under a colluding adversary, and behind a pre-aggregation,

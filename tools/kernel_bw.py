@@ -470,6 +470,62 @@ def mix_rows_compare(rounds=3):
         del x, second
 
 
+def sign_majority_compare(rounds=3):
+    """signSGD with majority vote: sign_pack on one 11.2M-element row (4 B read + 0.25 B
+    written per element) and sign_majority on the packed 24 x 11.2M and 64 x 11.2M blocks
+    (P/4 B read + 4 B written per element), each against the torch route to the same
+    result on the fp32 rows: torch.sign(x) for one row (what a worker would send
+    unpacked), torch.sign(x).sum(0).sign() for the vote.  The vote's arms read different
+    bytes on purpose (that is the point of the wire format): each arm's GB/s counts its
+    own minimum traffic, the time is the comparison.  x is randn with zeros, NaN and Inf
+    sprinkled in; the kernels' result is compared with the torch route first (NaN -> 0
+    in it); the arms alternate inside each round; min-max over the rounds per arm."""
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    times, order = {}, []
+    for rows in (24, 64):
+        x = torch.randn(rows, d, device=DEV)
+        x[:, ::7] = 0.0
+        x[::2, ::1001] = float("nan")
+        x[1::2, ::1003] = float("-inf")
+        packed = torch.empty(rows, d // 16, dtype=torch.int32, device=DEV)
+        out = torch.empty(d, device=DEV)
+        for p in range(rows):
+            ops.sign_pack(x[p], packed[p])
+        ops.sign_majority(packed, out)
+        ref = torch.nan_to_num(torch.sign(x), nan=0.0).sum(0).sign()
+        torch.cuda.synchronize()
+        assert bool((out == ref).all()) and bool((out.view(torch.int32) != -2 ** 31).all())
+        del ref
+        arms = [
+            (f"sign_majority ({rows} packed rows)", lambda: ops.sign_majority(packed, out),
+             rows * d // 4 + 4 * d, dict(iters=5000, warmup=100)),
+            (f"torch sign.sum.sign ({rows} fp32 rows)", lambda: torch.sign(x).sum(0).sign(),
+             2 * 4 * rows * d + 4 * rows * d + 12 * d, dict(iters=100, warmup=5)),
+        ]
+        if rows == 24:
+            arms += [
+                ("sign_pack (one 11.2M row)", lambda: ops.sign_pack(x[0], packed[0]),
+                 4 * d + d // 4, dict(iters=10000, warmup=100)),
+                ("torch.sign (one 11.2M row)", lambda: torch.sign(x[0]), 8 * d,
+                 dict(iters=10000, warmup=100)),
+            ]
+        for r in range(rounds):
+            print(f"# round {r}")
+            for name, fn, nbytes, kw in arms:
+                ms = t_ms(fn, **kw)
+                if name not in times:
+                    times[name] = []
+                    order.append(name)
+                times[name].append(ms)
+                report(name, ms, nbytes)
+        del x, packed
+    print("# min - max over rounds")
+    for name in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -602,6 +658,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("NNM_ONLY") == "1":
         mix_rows_compare()
+        raise SystemExit(0)
+    if os.environ.get("SIGN_ONLY") == "1":
+        sign_majority_compare()
         raise SystemExit(0)
     if os.environ.get("BULYAN_ONLY") == "1":
         bulyan_compare()
