@@ -39,13 +39,19 @@ class Config:
     adversarial: int = 1              # parity flag (err magnitude switch; reference hardcodes -100)
     worker_fail: int = 2
     group_size: int = 5
-    compress_grad: str = "none"       # none|bf16|sign wire format of the gradient exchange (bf16
+    compress_grad: str = "none"       # none|bf16|sign|mx8 wire format of the gradient exchange (bf16
                                       # replaces the reference's blosc/snappy CPU compression,
                                       # SURVEY §2.2 K12, for maj_vote / cyclic; sign is signSGD
                                       # with majority vote, arXiv:1810.05291: 2 bits per element,
                                       # baseline approach, mode normal, colocated topology, at
                                       # most 64 workers; the step is lr per coordinate; see
-                                      # parallel/aggregators.SignMajorityAggregator)
+                                      # parallel/aggregators.SignMajorityAggregator; mx8 is the
+                                      # MXFP8 block-scaled wire, one E4M3 byte per element and
+                                      # one power-of-two scale per 32: every baseline rule,
+                                      # alie/ipm, nnm and worker momentum run behind it;
+                                      # baseline approach, colocated topology; mode normal
+                                      # becomes the exchange-path mean, at most 64 workers;
+                                      # see parallel/aggregators.Aggregator.wire)
     checkpoint_step: int = 0
     optimizer: str = "sgd"            # sgd|adam (fused flat kernels, optim/flat_sgd.py)
 
@@ -126,6 +132,21 @@ class Config:
                     what + "cannot be combined with --pre-aggregation "
                     f"{self.pre_aggregation} (it mixes an fp32 exchanged block)")
 
+        if self.compress_grad == "mx8":
+            what = ("compress-grad 'mx8' (the MXFP8 block-scaled 8-bit wire of the baseline "
+                    "rules): ")
+            if self.approach != "baseline":
+                raise ValueError(
+                    what + "needs --approach baseline (one code quantum is 6% relative, far "
+                    "outside the vote tolerance of maj_vote and the locator thresholds of "
+                    f"cyclic), got {self.approach!r}")
+            if self.topology == "ps":
+                raise ValueError(what + "needs the colocated topology, not --topology ps")
+            if self.health_timeout > 0:
+                raise ValueError(
+                    what + "cannot be combined with --health-timeout (the packed exchange "
+                    "of a survivor world is not built)")
+
         if self.pre_aggregation != "none":
             what = f"pre-aggregation {self.pre_aggregation!r}: "
             if self.pre_aggregation != "nnm":
@@ -193,7 +214,8 @@ class Config:
 _HELP = {
     "compress_grad": "none | bf16 (alias compress: bf16 wire for maj_vote / cyclic) | sign "
                      "(signSGD with majority vote: 2-bit sign wire, --approach baseline --mode "
-                     "normal)",
+                     "normal) | mx8 (MXFP8 block-scaled 8-bit wire: E4M3 codes, one scale per "
+                     "32 elements; every --approach baseline rule, colocated topology)",
 }
 
 

@@ -21,6 +21,9 @@ __all__ = [
     "mix_rows_",
     "sign_pack",
     "sign_majority",
+    "mx8_pack",
+    "mx8_unpack",
+    "mx8_chunk_bytes",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -176,6 +179,36 @@ def sign_majority(packed, out):
         ext.sign_majority(packed, out)
         return
     fallback.sign_majority(packed, out)
+
+
+def mx8_chunk_bytes(chunk):
+    """Bytes of one packed record of the mx8 wire: chunk + round_up(chunk / 32, 16)."""
+    return fallback.mx8_chunk_bytes(int(chunk))
+
+
+def mx8_pack(g, out, chunk):
+    """The MXFP8 wire format: out (n / chunk * mx8_chunk_bytes(chunk),) uint8 = the packed
+    records of g (n,) fp32, n % chunk == 0, chunk % 64 == 0: one E4M3 code per element and
+    one E8M0 scale per 32 elements, NaN / Inf kept non-finite.  A record depends on its
+    chunk alone.  The kernel (gfx950 scaled FP8 converts, block amax by DPP) and the
+    fallback write the same bytes.  Format: above k_mx8_pack in draco_kernels.hip;
+    definition and checks: fallback.mx8_pack."""
+    ext = _native_for(g)
+    if ext is not None:
+        ext.mx8_pack(g, out, int(chunk))
+        return
+    fallback.mx8_pack(g, out, int(chunk))
+
+
+def mx8_unpack(packed, out):
+    """out (P, chunk) fp32 = the decoded rows of packed (P, mx8_chunk_bytes(chunk)) uint8.
+    Every byte pattern decodes to an fp32 value, NaN or +-Inf; kernel and fallback agree
+    bit for bit (NaNs as NaNs).  Definition and checks: fallback.mx8_unpack."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx8_unpack(packed, out)
+        return
+    fallback.mx8_unpack(packed, out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

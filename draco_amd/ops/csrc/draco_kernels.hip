@@ -16,6 +16,8 @@
 // mixing, Y = W X in place) is the one kernel on the matrix unit (fp32 MFMA).
 // k_sign_pack / k_sign_majority (signSGD with majority vote) are the bit kernels: wave
 // ballots pack two sign bits per element, bit-sliced counters vote on 64 elements at once.
+// k_mx8_pack / k_mx8_unpack (the MXFP8 block-scaled wire) convert with the gfx950 scaled
+// FP8 instructions; the block scale is reduced across eight lanes by DPP.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -1775,6 +1777,232 @@ void sign_majority(torch::Tensor packed, torch::Tensor out) {
   }
 }
 
+// --------------------------------------------------------------------------- mx8 wire
+// An 8-bit block-scaled wire format for gradient rows: OCP Microscaling MXFP8, E4M3
+// elements with one E8M0 scale per 32 elements.  Unlike the sign wire it keeps magnitudes:
+// it decodes to an ordinary fp32 block, so every rule reads it unchanged.
+//
+// WIRE FORMAT (the one description; fallback.mx8_pack / mx8_unpack produce the same bytes).
+// Element code: one byte, OCP FP8 E4M3 ("e4m3fn"): 1 sign, 4 exponent (bias 7), 3 mantissa
+// bits; no infinities, 0x7F / 0xFF are NaN, the largest magnitude is 448 (0x7E),
+// subnormals step by 2^-9.  Block: 32 consecutive elements of a row share a scale byte s,
+// an E8M0 exponent meaning 2^(s-127); s = 0xFF is NaN for the whole block.
+//   Encoding a block: amax = the largest |x| over its FINITE elements; e = the smallest
+// integer with amax / 2^e <= 448, read off amax's bits: e = exponent(amax) - 8, plus 1 if the
+// mantissa field exceeds 0x600000 (448 = 1.75 * 2^8); e is clamped to >= -117 (also taken
+// when no element is finite or amax = 0) and s = e + 127, so an encoder emits s in
+// [10, 247].  A finite element becomes the code nearest to x / 2^e, ties to the even code,
+// with x's sign bit (-0.0 and values that round to zero keep it); by the choice of e nothing
+// saturates.  NaN, +Inf and -Inf become the NaN code 0x7F with the element's sign bit and
+// do not influence the scale.
+//   Decoding: s = 0xFF gives NaN for the whole block; otherwise s is clamped to >= 10 and
+// value = code value * 2^(s-127) in fp32, NaN codes giving NaN.  With the clamp every
+// finite non-zero result is a normal fp32 number (2^-9 * 2^-117 = 2^-126), so flushing
+// denormals changes nothing; an overflowing product (s >= 247 with large codes) is +-Inf.
+// Every byte pattern decodes to an fp32 value, NaN or +-Inf.
+//   Packed row: a row of n elements is packed against a chunk (the shard length) with
+// n % chunk == 0 and chunk % 64 == 0, into n / chunk records of
+// chunk_bytes = chunk + round_up(chunk / 32, 16) bytes: the chunk code bytes, the chunk / 32
+// scale bytes, zero padding.  Records and scale runs start 16-byte aligned, a record
+// depends on its chunk's elements alone, and the even all_to_all split of a packed row
+// lands each rank's codes and scales on it.
+//   Error: for finite x in a block of scale X = 2^e, |decode(encode(x)) - x| <=
+// max(2^-4 |x|, 2^-10 X), and X < amax / 224.
+//
+// The gfx950 scaled converts (v_cvt_scalef32_pk_fp8_f32 / v_cvt_scalef32_pk_f32_fp8) do the
+// element work.  Measured once on the MI355X with a stand-alone probe program that is not in
+// the tree (the exact tests of tests/test_mx8_gpu.py are what stays), against the integer
+// statement of the format, over every fp32 bit pattern that is in range for scales 10, 11,
+// 60, 127, 200, 246, 247 and
+// over every (code, scale) pair: the encode gives the format's byte for every finite input
+// (nearest, ties to even, fp32 subnormal inputs honoured, FP8 subnormal outputs produced,
+// sign of zero kept); for NaN it does not keep the sign bit (+NaN came out as 0xFF), so
+// non-finite elements are patched with an integer select; the decode is exact for all 256
+// codes at every scale 10..254, NaN codes and the overflow to +-Inf included.  The scale
+// operand is the fp32 number 2^(s-127), always normal here.  Out-of-range inputs are never
+// converted, so what the instruction does with them is not relied on.
+//
+// Both kernels walk "units": a unit is one wave-wide load of 256 consecutive elements of one
+// record (a float4, or a dword of codes, per lane), MX8_TRIP units per wave per trip with
+// all loads issued before any conversion.  chunk % 64 == 0: a lane's four elements and a
+// 32-element block (eight adjacent lanes) are inside or outside the record as a whole.
+#define MX8_TRIP 4
+typedef short mx8_v2s __attribute__((ext_vector_type(2)));
+typedef float mx8_v2f __attribute__((ext_vector_type(2)));
+
+static inline long mx8_chunk_bytes(long chunk) { return chunk + (chunk / 32 + 15) / 16 * 16; }
+
+// max over the eight lanes of a block, in every one of them: two quad permutes and a mirror
+// of the 8-lane half row, on the VALU's data path (no LDS, no ds_bpermute)
+__device__ __forceinline__ unsigned mx8_block_max(unsigned v) {
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));   // lane ^ 1
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));   // lane ^ 2
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));  // 7 - lane
+  return v;
+}
+
+// k_mx8_pack: one streaming pass, 4 B read and ~1.03 B written per element, no LDS, no
+// atomics.  Per unit: the finite amax of a lane's float4 (integer max of the magnitude
+// bits), the block max by DPP, the scale byte from amax's exponent and mantissa fields, two
+// scaled converts for the lane's dword of codes (a wave stores 256 contiguous bytes).  The
+// eight scale bytes of a unit are collected from lanes 0, 8, .., 56 with v_readlane into two
+// dwords, and lane 0 stores them as one 8-byte vector; an outside block contributes 0, which
+// is the record's padding, and the unit that ends a record with an odd unit count also
+// writes the 8 zero bytes that complete the padded scale run (round_up(chunk/32, 16)).
+// The loop's trip count is wave-uniform: every lane runs the DPP and readlane steps.
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_pack(const uint4 *__restrict__ g, unsigned char *__restrict__ out, long chunk, long cbytes,
+           int upr, int units) {
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  long u0 = (blockIdx.x * (long)(NTHREADS / WAVE) + wave) * MX8_TRIP;
+  long ustride = gridDim.x * (long)(NTHREADS / WAVE) * MX8_TRIP;
+  for (; u0 < units; u0 += ustride) {
+    // u0 < units fits an int (checked on the host): a 32-bit division, once per trip
+    const int u = (int)u0;
+    int r = u / upr, j = u - r * upr;  // record, unit of the record
+    uint4 v[MX8_TRIP];
+    long base[MX8_TRIP];  // byte offset of the unit's record; -1: no such unit
+    int uj[MX8_TRIP];
+#pragma unroll
+    for (int t = 0; t < MX8_TRIP; ++t) {
+      long o = (long)j * 256 + 4 * lane;  // the lane's first element in the record
+      base[t] = u0 + t < units ? r * cbytes : -1;
+      uj[t] = j;
+      v[t] = make_uint4(0u, 0u, 0u, 0u);
+      if (base[t] >= 0 && o < chunk) v[t] = g[(r * chunk + o) / 4];
+      if (++j == upr) { j = 0; ++r; }
+    }
+#pragma unroll
+    for (int t = 0; t < MX8_TRIP; ++t) {
+      long o = (long)uj[t] * 256 + 4 * lane;
+      bool in = base[t] >= 0 && o < chunk;
+      unsigned x[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
+      unsigned amax = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        unsigned a = x[k] & 0x7fffffffu;
+        amax = max(amax, a < 0x7f800000u ? a : 0u);
+      }
+      amax = mx8_block_max(amax);
+      int s = (int)(amax >> 23) - 8 + ((amax & 0x7fffffu) > 0x600000u);
+      s = max(s, 10);
+      float scale = __uint_as_float((unsigned)s << 23);
+      mx8_v2s w = {0, 0};
+      w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, __uint_as_float(x[0]), __uint_as_float(x[1]),
+                                                   scale, false);
+      w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, __uint_as_float(x[2]), __uint_as_float(x[3]),
+                                                   scale, true);
+      unsigned codes = __builtin_bit_cast(unsigned, w);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)  // NaN, +-Inf: the NaN code with the element's sign
+        if ((x[k] & 0x7fffffffu) >= 0x7f800000u)
+          codes = (codes & ~(0xffu << (8 * k))) | ((0x7fu | (x[k] >> 24 & 0x80u)) << (8 * k));
+      if (in) *reinterpret_cast<unsigned *>(out + base[t] + o) = codes;
+      int sb = in ? s : 0;
+      unsigned lo = 0u, hi = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        lo |= (unsigned)__builtin_amdgcn_readlane(sb, 8 * k) << (8 * k);
+        hi |= (unsigned)__builtin_amdgcn_readlane(sb, 32 + 8 * k) << (8 * k);
+      }
+      if (lane == 0 && base[t] >= 0) {
+        unsigned char *sp = out + base[t] + chunk + 8L * uj[t];
+        *reinterpret_cast<uint2 *>(sp) = make_uint2(lo, hi);
+        if (uj[t] == upr - 1 && (upr & 1)) *reinterpret_cast<uint2 *>(sp + 8) = make_uint2(0u, 0u);
+      }
+    }
+  }
+}
+
+// k_mx8_unpack: 1 B read and 4 B written per element.  A unit is 256 codes of one packed
+// row: a lane reads its dword of codes (256 contiguous bytes per wave) and its block's scale
+// byte (one byte shared by eight lanes, a cached byte load), converts with two scaled
+// converts and writes one float4 (1 KB contiguous per wave).  The rows are flattened into
+// the unit index.  No cross-lane step, so an outside lane simply skips.
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_unpack(const unsigned char *__restrict__ packed, float4 *__restrict__ out, long chunk,
+             long cbytes, int upr, int units) {
+  const int lane = threadIdx.x % WAVE;
+  long u0 = (blockIdx.x * (long)(NTHREADS / WAVE) + threadIdx.x / WAVE) * MX8_TRIP;
+  long ustride = gridDim.x * (long)(NTHREADS / WAVE) * MX8_TRIP;
+  for (; u0 < units; u0 += ustride) {
+    const int u = (int)u0;  // as in k_mx8_pack
+    int r = u / upr, j = u - r * upr;
+    unsigned codes[MX8_TRIP], sbyte[MX8_TRIP];
+    long dst[MX8_TRIP];  // float4 index in out; -1: nothing to do
+#pragma unroll
+    for (int t = 0; t < MX8_TRIP; ++t) {
+      long o = (long)j * 256 + 4 * lane;
+      bool in = u0 + t < units && o < chunk;
+      dst[t] = in ? (r * chunk + o) / 4 : -1;
+      codes[t] = sbyte[t] = 0u;
+      if (in) {
+        const unsigned char *rec = packed + r * cbytes;
+        codes[t] = *reinterpret_cast<const unsigned *>(rec + o);
+        sbyte[t] = rec[chunk + o / 32];
+      }
+      if (++j == upr) { j = 0; ++r; }
+    }
+#pragma unroll
+    for (int t = 0; t < MX8_TRIP; ++t) {
+      float scale = __uint_as_float(max(sbyte[t], 10u) << 23);
+      mx8_v2f a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes[t], scale, false);
+      mx8_v2f b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes[t], scale, true);
+      float4 y = make_float4(a.x, a.y, b.x, b.y);
+      if (sbyte[t] == 0xffu) y.x = y.y = y.z = y.w = __uint_as_float(0x7fc00000u);
+      if (dst[t] >= 0) out[dst[t]] = y;
+    }
+  }
+}
+
+// the checks shared by mx8_pack and mx8_unpack; returns the units (wave loads) of the call
+static inline int check_mx8(const char *op, const torch::Tensor &vals, const torch::Tensor &bytes,
+                            long chunk, long records) {
+  CHECK_IN(vals);
+  CHECK_IN(bytes);
+  TORCH_CHECK(vals.device() == bytes.device(), op, ": tensors must be on one device");
+  TORCH_CHECK(vals.scalar_type() == torch::kFloat32, op, ": values must be fp32");
+  TORCH_CHECK(bytes.scalar_type() == torch::kUInt8, op, ": packed data must be uint8");
+  TORCH_CHECK(chunk >= 0 && chunk % 64 == 0, op, ": chunk must be a multiple of 64, got ", chunk);
+  TORCH_CHECK(vals.numel() == records * chunk, op, ": values must hold ", records, " x ", chunk,
+              " elements, got ", vals.numel());
+  TORCH_CHECK(bytes.numel() == records * mx8_chunk_bytes(chunk), op, ": packed data must hold ",
+              records, " records of ", mx8_chunk_bytes(chunk), " bytes, got ", bytes.numel());
+  TORCH_CHECK((uintptr_t)vals.data_ptr() % 16 == 0 && (uintptr_t)bytes.data_ptr() % 16 == 0, op,
+              ": tensors must be 16-byte aligned");
+  long units = records * ((chunk + 255) / 256);
+  TORCH_CHECK(units <= 0x7fffffffL - MX8_TRIP, op, ": ", units, " wave loads exceed the 32-bit unit index");
+  return (int)units;
+}
+
+void mx8_pack(torch::Tensor g, torch::Tensor out, long chunk) {
+  long n = g.numel();
+  TORCH_CHECK(g.dim() == 1 && out.dim() == 1, "mx8_pack: g and out must be 1D");
+  TORCH_CHECK(chunk > 0 ? n % chunk == 0 : n == 0, "mx8_pack: length ", n,
+              " is not a multiple of chunk ", chunk);
+  int units = check_mx8("mx8_pack", g, out, chunk, chunk > 0 ? n / chunk : 0);
+  if (units == 0) return;
+  int upr = (int)((chunk + 255) / 256);
+  int blocks = n_blocks((units + MX8_TRIP - 1) / MX8_TRIP, NTHREADS / WAVE);
+  launch(k_mx8_pack, dim3(blocks), 0, (const uint4 *)g.data_ptr<float>(), out.data_ptr<uint8_t>(),
+         chunk, mx8_chunk_bytes(chunk), upr, units);
+}
+
+void mx8_unpack(torch::Tensor packed, torch::Tensor out) {
+  TORCH_CHECK(packed.dim() == 2 && out.dim() == 2 && packed.size(0) == out.size(0),
+              "mx8_unpack: packed must be (P, chunk_bytes) and out (P, chunk)");
+  long P = out.size(0), chunk = out.size(1);
+  int units = check_mx8("mx8_unpack", out, packed, chunk, P);
+  TORCH_CHECK(packed.size(1) == mx8_chunk_bytes(chunk), "mx8_unpack: packed rows must have ",
+              mx8_chunk_bytes(chunk), " bytes for chunk ", chunk, ", got ", packed.size(1));
+  if (units == 0) return;  // P = 0 or chunk = 0: no launch
+  int upr = (int)((chunk + 255) / 256);
+  int blocks = n_blocks((units + MX8_TRIP - 1) / MX8_TRIP, NTHREADS / WAVE);
+  launch(k_mx8_unpack, dim3(blocks), 0, packed.data_ptr<uint8_t>(), (float4 *)out.data_ptr<float>(),
+         chunk, mx8_chunk_bytes(chunk), upr, units);
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -1807,4 +2035,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mix_rows", &mix_rows);
   m.def("sign_pack", &sign_pack);
   m.def("sign_majority", &sign_majority);
+  m.def("mx8_pack", &mx8_pack);
+  m.def("mx8_unpack", &mx8_unpack);
 }

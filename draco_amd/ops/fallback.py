@@ -391,6 +391,89 @@ def sign_majority(packed: torch.Tensor, out: torch.Tensor) -> None:
     out.copy_(torch.sign(diff))
 
 
+# --------------------------------------------------------------------- mx8 wire
+def mx8_chunk_bytes(chunk: int) -> int:
+    """Bytes of one packed record: chunk codes, chunk/32 scales, zero padding to 16."""
+    return chunk + (chunk // 32 + 15) // 16 * 16
+
+
+def _check_mx8(op: str, vals: torch.Tensor, data: torch.Tensor, chunk: int, records: int) -> None:
+    if vals.dtype != torch.float32:
+        raise ValueError(f"{op}: values must be fp32, got {vals.dtype}")
+    if data.dtype != torch.uint8:
+        raise ValueError(f"{op}: packed data must be uint8, got {data.dtype}")
+    if not vals.is_contiguous() or not data.is_contiguous():
+        raise ValueError(f"{op}: tensors must be contiguous")
+    if vals.device != data.device:
+        raise ValueError(f"{op}: tensors must be on one device")
+    if chunk < 0 or chunk % 64 != 0:
+        raise ValueError(f"{op}: chunk must be a multiple of 64, got {chunk}")
+    if vals.numel() != records * chunk:
+        raise ValueError(f"{op}: values must hold {records} x {chunk} elements, got "
+                         f"{vals.numel()}")
+    if data.numel() != records * mx8_chunk_bytes(chunk):
+        raise ValueError(f"{op}: packed data must hold {records} records of "
+                         f"{mx8_chunk_bytes(chunk)} bytes, got {data.numel()}")
+
+
+@torch.no_grad()
+def mx8_pack(g: torch.Tensor, out: torch.Tensor, chunk: int) -> None:
+    """The MXFP8 wire (E4M3 codes, one E8M0 scale per 32 elements): out = the n / chunk
+    packed records of g.  g: (n,) fp32, n % chunk == 0, chunk % 64 == 0; out:
+    (n / chunk * mx8_chunk_bytes(chunk),) uint8.  The format is described once, above
+    k_mx8_pack in draco_kernels.hip; this is its executable definition, in integer
+    arithmetic on the fp32 bit patterns, and the kernel writes the same bytes."""
+    n = g.numel()
+    if g.dim() != 1 or out.dim() != 1:
+        raise ValueError("mx8_pack: g and out must be 1D")
+    if (n % chunk != 0) if chunk > 0 else (n != 0):
+        raise ValueError(f"mx8_pack: length {n} is not a multiple of chunk {chunk}")
+    records = n // chunk if chunk > 0 else 0
+    _check_mx8("mx8_pack", g, out, chunk, records)
+    if n == 0:
+        return
+    u = g.view(torch.int32).to(torch.int64)
+    a, sign = u & 0x7FFFFFFF, (u >> 24) & 0x80
+    fin = a < 0x7F800000
+    amax = torch.where(fin, a, torch.zeros_like(a)).view(-1, 32).amax(dim=1)
+    # s = e + 127 with e = exponent(amax) - 8, plus 1 past 1.75 * 2^exponent; e >= -117
+    s = ((amax >> 23) - 8 + ((amax & 0x7FFFFF) > 0x600000)).clamp_(min=10)
+    ex, m = a >> 23, a & 0x7FFFFF
+    m = torch.where(ex > 0, m | 0x800000, m)  # the 24-bit significand; subnormals have ex = 1
+    q = ex.clamp(min=1) - s.repeat_interleave(32)  # exponent of x / 2^e
+    # normal codes keep 4 significand bits (drop 20); below 2^-6 the codes step by 2^-9
+    sh = (20 + (-6 - q).clamp(min=0)).clamp(max=31)
+    r = (m + (torch.ones_like(sh) << (sh - 1)) - 1 + ((m >> sh) & 1)) >> sh  # nearest, ties to even
+    code = ((q + 6).clamp(min=0) << 3) + r  # r = 16 carries into the exponent field
+    code = torch.where(fin, code, torch.full_like(code, 0x7F)) | sign
+    rec = out.view(records, -1)
+    rec[:, :chunk] = code.view(records, chunk).to(torch.uint8)
+    rec[:, chunk: chunk + chunk // 32] = s.view(records, -1).to(torch.uint8)
+    rec[:, chunk + chunk // 32:] = 0
+
+
+@torch.no_grad()
+def mx8_unpack(packed: torch.Tensor, out: torch.Tensor) -> None:
+    """out (P, chunk) fp32 = the decoded rows of packed (P, mx8_chunk_bytes(chunk)) uint8 in
+    mx8_pack's format.  Any bytes decode: a scale byte below 10 counts as 10, 0xFF makes the
+    block NaN, an overflowing product is +-Inf.  P == 0 or chunk == 0 returns at once."""
+    if packed.dim() != 2 or out.dim() != 2 or packed.shape[0] != out.shape[0]:
+        raise ValueError("mx8_unpack: packed must be (P, chunk_bytes) and out (P, chunk)")
+    P, chunk = out.shape
+    _check_mx8("mx8_unpack", out, packed, chunk, P)
+    if P == 0 or chunk == 0:
+        return
+    c = torch.arange(256, device=out.device)
+    e, m = (c >> 3) & 15, (c & 7).float()
+    table = torch.where(e > 0, torch.ldexp(1.0 + m / 8.0, e - 7), m * 2.0 ** -9)
+    table = torch.where((c & 0x7F) == 0x7F, torch.full_like(table, float("nan")), table)
+    table = torch.where(c >= 128, -table, table)
+    s = packed[:, chunk: chunk + chunk // 32].to(torch.int32)
+    scale = (s.clamp(min=10) << 23).view(torch.float32)  # 2^(s-127), a normal fp32 number
+    scale = torch.where(s == 0xFF, torch.full_like(scale, float("nan")), scale)
+    out.copy_(table[packed[:, :chunk].long()] * scale.repeat_interleave(32, dim=1))
+
+
 # --------------------------------------------------------------------- vote
 @torch.no_grad()
 def rows_equal(x: torch.Tensor, a_idx: torch.Tensor, b_idx: torch.Tensor, atol: float) -> torch.Tensor:

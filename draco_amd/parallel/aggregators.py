@@ -73,6 +73,17 @@ class Aggregator:
     # the first kernel launch on the GPU
     MAX_WORKERS = None
     MAX_WORKERS_WHY = ""
+    # "mx8" (set by build_baseline_aggregator for --compress-grad mx8): the rows travel in
+    # the MXFP8 block-scaled format of ops.mx8_pack / ops.mx8_unpack, one E4M3 byte per
+    # element and one shared power-of-two scale per 32 (3.9x fewer all_to_all bytes than
+    # fp32).  start_row packs the payload row into a persistent (rows, world * chunk_bytes)
+    # uint8 send buffer and posts its all_to_all into a (rows, world, chunk_bytes) receive
+    # buffer; _exchange drains and decodes with ONE kernel into a persistent (rows * world,
+    # shard) fp32 block, which collusion, mixing and every rule read as they read the fp32
+    # exchange.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
+    # stays non-finite.  With one rank the rows are still packed and unpacked.  The
+    # bucketed path is not built for this wire: the row ships whole from aggregate().
+    wire = None
 
     def __init__(self, comm: Communicator, space: FlatSpace, comm_dtype=torch.float32):
         self.comm = comm
@@ -101,7 +112,25 @@ class Aggregator:
                 self._recv32 = torch.empty(rows, self.comm.world, self.space.shard,
                                            dtype=torch.float32, device=device)
 
+    def _start_row_mx8(self, payload: torch.Tensor, row: int) -> None:
+        rows, world, shard = payload.shape[0], self.comm.world, self.space.shard
+        if self._send is None or self._send.shape[0] != rows:
+            cb, dev = ops.mx8_chunk_bytes(shard), payload.device
+            self._send = torch.empty(rows, world * cb, dtype=torch.uint8, device=dev)
+            # one rank: the packed rows are the received block
+            self._recv = (torch.empty(rows, world, cb, dtype=torch.uint8, device=dev)
+                          if self.comm.distributed else self._send)
+            self._recv32 = torch.empty(rows * world, shard, dtype=torch.float32, device=dev)
+        ops.mx8_pack(payload[row], self._send[row], shard)
+        if self.comm.distributed:
+            w = self.comm.all_to_all_row(self._send[row], self._recv[row], async_op=True)
+            if w is not None:
+                self._works.append(w)
+        self._started.add(row)
+
     def start_row(self, payload: torch.Tensor, row: int) -> None:
+        if self.wire == "mx8":
+            return self._start_row_mx8(payload, row)
         if not self.comm.distributed:
             return
         self._ensure_recv(payload.shape[0], payload.device)
@@ -122,7 +151,7 @@ class Aggregator:
         isends).  Same wire format as start_row, delivered into the same recv slots;
         the trainer calls mark_row_started(row) once every bucket of the row is
         posted."""
-        if not self.comm.distributed:
+        if not self.comm.distributed or self.wire == "mx8":
             return
         self._ensure_recv(payload.shape[0], payload.device)
         world, shard, rank = self.comm.world, self.space.shard, self.comm.rank
@@ -142,7 +171,8 @@ class Aggregator:
             self._pending_copies.append((tmp.view(world, m), row, mlo - rank * shard, mhi - rank * shard))
 
     def mark_row_started(self, row: int) -> None:
-        self._started.add(row)
+        if self.wire != "mx8":
+            self._started.add(row)
 
     def exchanged(self, payload: torch.Tensor) -> torch.Tensor:
         """(rows, d_pad) payload -> (rows*world, shard) in l-major row order.  With a
@@ -176,6 +206,11 @@ class Aggregator:
 
     def _exchange(self, payload: torch.Tensor) -> torch.Tensor:
         rows = payload.shape[0]
+        if self.wire == "mx8":
+            self._start_rest(payload)
+            self._drain()
+            ops.mx8_unpack(self._recv.view(self._recv32.shape[0], -1), self._recv32)
+            return self._recv32
         if not self.comm.distributed:
             return payload.view(rows, self.space.shard)
         self._start_rest(payload)
@@ -1063,14 +1098,15 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
                 f"got mode {cfg.mode!r}, err mode {cfg.err_mode!r}, pre-aggregation "
                 f"{cfg.pre_aggregation!r}")
         return SignMajorityAggregator(comm, space, num_workers=num_workers)
-    if cfg.mode == "normal" and (cfg.err_mode in COLLUDING_MODES or nnm):
+    mx8 = cfg.compress_grad == "mx8"
+    if cfg.mode == "normal" and (cfg.err_mode in COLLUDING_MODES or nnm or mx8):
         # MeanAggregator sums inside the reduce-scatter: the honest rows are never
-        # visible together.  Under a colluding adversary, and behind a pre-aggregation,
-        # the plain mean goes over the exchange path instead: the trimmed mean with
-        # nothing trimmed.
+        # visible together, and a sum on the wire cannot carry a quantised format.  Under
+        # a colluding adversary, behind a pre-aggregation and on the mx8 wire the plain
+        # mean goes over the exchange path instead: the trimmed mean with nothing trimmed.
         cls, kwargs, name = TrimmedMeanAggregator, {"trim": 0}, "mean"
         why = (f"the colluding err mode {cfg.err_mode!r}" if cfg.err_mode in COLLUDING_MODES
-               else "--pre-aggregation nnm")
+               else "--pre-aggregation nnm" if nnm else "--compress-grad mx8")
         hint = (f" (mode 'normal' under {why} is the "
                 "trim=0 mean over the exchange path, so that kernel's limit of 64 workers "
                 "applies)")
@@ -1084,6 +1120,8 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
         raise ValueError(f"{e}{hint}") from None
     if name is not None:
         agg.name = name
+    if mx8:
+        agg.wire = "mx8"  # see Aggregator.wire: every rule reads the decoded block
     if nnm:
         from .mixing import NearestNeighborMixing  # mixing imports this module
 

@@ -526,6 +526,79 @@ def sign_majority_compare(rounds=3):
         print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def mx8_compare(rounds=3):
+    """The MXFP8 wire: mx8_pack on one 11.2M-element row (4 B read + 1.03 B written per
+    element) and mx8_unpack on the packed 24 x 11.2M and 64 x 11.2M blocks (1.03 B read +
+    4 B written), each beside the torch route the bf16 wire uses at the same element count:
+    copy_ fp32 -> bf16 for one row (6 B per element), copy_ bf16 -> fp32 for the block (6 B).
+    Each arm's GB/s counts its own bytes; the time is the comparison.  Timed with events
+    around `iters` back-to-back launches after a warm-up; the kernels' results are compared
+    with the fallback's torch statement on the device first; the arms alternate inside each
+    round; min-max over the rounds per arm."""
+    from draco_amd.ops import fallback as fb
+    d = 11_173_952
+    d = (d + 63) // 64 * 64
+    cb = ops.mx8_chunk_bytes(d)
+
+    def ev_ms(fn, iters, warmup):
+        for _ in range(warmup):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters
+
+    times, order = {}, []
+    for rows in (24, 64):
+        x = torch.randn(d, device=DEV) * 1e-2
+        x[::1001] = float("nan")
+        packed = torch.empty(rows, cb, dtype=torch.uint8, device=DEV)
+        for p in range(rows):
+            ops.mx8_pack(x, packed[p], d)
+        ref = torch.empty(cb, dtype=torch.uint8, device=DEV)
+        fb.mx8_pack(x, ref, d)
+        assert bool((packed[rows - 1] == ref).all())
+        out = torch.empty(rows, d, device=DEV)
+        ops.mx8_unpack(packed, out)
+        yref = torch.empty(1, d, device=DEV)
+        fb.mx8_unpack(ref.view(1, -1), yref)
+        nan = torch.isnan(yref[0])
+        assert bool((torch.isnan(out[rows - 1]) == nan).all())
+        assert bool((out[rows - 1][~nan] == yref[0][~nan]).all())
+        del ref, yref, nan
+        h = torch.empty(rows, d, dtype=torch.bfloat16, device=DEV)
+        arms = [
+            (f"mx8_unpack ({rows} x 11.2M)", lambda: ops.mx8_unpack(packed, out),
+             rows * (cb + 4 * d), dict(iters=200, warmup=20)),
+            (f"copy_ bf16->fp32 ({rows} x 11.2M)", lambda: out.copy_(h), rows * 6 * d,
+             dict(iters=200, warmup=20)),
+        ]
+        if rows == 24:
+            arms += [
+                ("mx8_pack (one 11.2M row)", lambda: ops.mx8_pack(x, packed[0], d), 4 * d + cb,
+                 dict(iters=2000, warmup=100)),
+                ("copy_ fp32->bf16 (one 11.2M row)", lambda: h[0].copy_(x), 6 * d,
+                 dict(iters=2000, warmup=100)),
+            ]
+        for r in range(rounds):
+            print(f"# round {r}")
+            for name, fn, nbytes, kw in arms:
+                ms = ev_ms(fn, **kw)
+                if name not in times:
+                    times[name] = []
+                    order.append((name, nbytes))
+                times[name].append(ms)
+                report(name, ms, nbytes)
+        del x, packed, out, h
+    print("# min - max over rounds, GB/s at the min")
+    for name, nbytes in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -661,6 +734,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("SIGN_ONLY") == "1":
         sign_majority_compare()
+        raise SystemExit(0)
+    if os.environ.get("MX8_ONLY") == "1":
+        mx8_compare()
         raise SystemExit(0)
     if os.environ.get("BULYAN_ONLY") == "1":
         bulyan_compare()
