@@ -24,6 +24,8 @@ __all__ = [
     "mx8_pack",
     "mx8_unpack",
     "mx8_chunk_bytes",
+    "mx8_column_trimmed_mean",
+    "mx8_column_mean_around",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -209,6 +211,29 @@ def mx8_unpack(packed, out):
         ext.mx8_unpack(packed, out)
         return
     fallback.mx8_unpack(packed, out)
+
+
+def mx8_column_trimmed_mean(packed, lo, hi, out):
+    """out (chunk,) fp32 = column_trimmed_mean(mx8_unpack(packed), lo, hi), bit for bit, for
+    packed (P, mx8_chunk_bytes(chunk)) uint8, P <= 64, chunk % 64 == 0.  On the GPU one kernel
+    reads the records themselves (a dword of codes is four columns of a lane) and the fp32
+    block is never formed.  Definition and checks: fallback.mx8_column_trimmed_mean."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx8_column_trimmed_mean(packed, int(lo), int(hi), out)
+        return
+    fallback.mx8_column_trimmed_mean(packed, int(lo), int(hi), out)
+
+
+def mx8_column_mean_around(packed, keep, clo, chi, out):
+    """out (chunk,) fp32 = column_mean_around(mx8_unpack(packed), keep, clo, chi), bit for
+    bit; shapes and kernel as mx8_column_trimmed_mean.  Definition and checks:
+    fallback.mx8_column_mean_around."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx8_column_mean_around(packed, int(keep), int(clo), int(chi), out)
+        return
+    fallback.mx8_column_mean_around(packed, int(keep), int(clo), int(chi), out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

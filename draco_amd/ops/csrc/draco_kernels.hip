@@ -17,7 +17,8 @@
 // k_sign_pack / k_sign_majority (signSGD with majority vote) are the bit kernels: wave
 // ballots pack two sign bits per element, bit-sliced counters vote on 64 elements at once.
 // k_mx8_pack / k_mx8_unpack (the MXFP8 block-scaled wire) convert with the gfx950 scaled
-// FP8 instructions; the block scale is reduced across eight lanes by DPP.
+// FP8 instructions; the block scale is reduced across eight lanes by DPP.  k_mx8_col is
+// the column sort on that wire: it reads the packed records, four columns per lane.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -2003,6 +2004,170 @@ void mx8_unpack(torch::Tensor packed, torch::Tensor out) {
          chunk, mx8_chunk_bytes(chunk), upr, units);
 }
 
+// --------------------------------------------------------------------------- mx8 column rules
+// mx8_column_trimmed_mean / mx8_column_mean_around: mx8_unpack followed by
+// column_trimmed_mean / column_mean_around, bit for bit, in one launch that reads the packed
+// records themselves: ~1.03 B per row and column instead of 1 B + 4 B written + 4 B read back,
+// and no (P, chunk) fp32 block anywhere.
+//
+// Work split.  A wave walks units of 256 consecutive columns (grid-stride over units, one
+// unit per wave per trip); a lane owns the FOUR adjacent columns 4*lane .. 4*lane+3 and per
+// row loads one dword of codes, 256 contiguous bytes per wave: a quarter of the load
+// instructions per column of k_col_trimmed_mean, whose layout and not whose sort bounds it.
+// The four columns lie in one 32-element block, so one scale per row serves them; it is
+// fetched as a per-lane byte load, as k_mx8_unpack does (eight lanes read the same byte, 8
+// contiguous bytes per wave and row: one cache line, no select by lane / 8 afterwards).  The
+// row base is wave-uniform and the lane offset 32-bit (checked on the host).  All P code
+// loads and all P scale loads of a unit are issued before the first conversion, behind the
+// same wave-uniform `p < P` tests as load_column's.
+//
+// Registers.  The codes stay packed: N dwords, and N scales.  Once the loads are in, a row's
+// scale byte becomes the fp32 operand 2^(max(s,10)-127) in place, and a NaN block (s = 0xFF)
+// is folded into the codes (all four become the NaN code), so the per-column work is the
+// convert and the NaN -> +inf select alone.  COLS columns are live at a time: one
+// v_cvt_scalef32_pk_f32_fp8 of the low half yields two columns, both are sorted and reduced
+// (sort_columns and mean_around_sorted, unchanged), then the codes shift down by 16 bits and
+// the loop runs again.  The loop is NOT unrolled: the convert's half select is an immediate,
+// so shifting the codes is what lets one copy of the sort network serve all four columns, and
+// the results rotate through a float4 (no run-time-indexed array).  COLS = 1 is the same
+// loop four times over one column with 8-bit shifts, for the padded sizes at which two
+// columns beside codes and scales do not fit (see mx8_cols).  s[] is indexed by compile-time
+// constants only; no instantiation uses scratch (profiles/kernel_bw_mx8_fused.txt).
+//
+// Output: one float4 per lane, 1 KB contiguous per wave.  chunk % 64 == 0, so a lane's four
+// columns are inside the record or outside as a whole; there is no cross-lane step, no LDS
+// and no atomics, so an outside lane of the unit that ends the shard simply skips.
+template <int N> constexpr int mx8_cols = N <= 32 ? 2 : 1;
+
+// ranks [lo, hi) of a sorted column, k_col_trimmed_mean's arithmetic
+template <int N>
+__device__ __forceinline__ float trimmed_sorted(const float (&s)[N], int lo, int hi, float cnt) {
+  float acc = -0.f;
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+    if (r >= lo && r < hi) acc += s[r];
+  return acc / cnt;
+}
+
+// AROUND: (a, b, c) = (keep, clo, chi), (f, g) = (ccnt, kcnt); else (a, b) = (lo, hi), f = cnt
+template <int N, int COLS, bool AROUND>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_col(const unsigned char *__restrict__ packed, int P, int a, int b, int c, float f, float g,
+          float4 *__restrict__ out, unsigned chunk, long cbytes, int units) {
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const int ustride = gridDim.x * (NTHREADS / WAVE);
+  constexpr bool PACK = COLS == 1;  // scale exponents four to a register
+  for (int u = blockIdx.x * (NTHREADS / WAVE) + wave; u < units; u += ustride) {
+    const unsigned o = (unsigned)u * 256u + 4u * lane;  // the lane's first column
+    if (o >= chunk) continue;
+    const unsigned so = chunk + o / 32;  // its block's scale byte
+    unsigned codes[N], sb[N];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      codes[p] = sb[p] = 0u;
+      if (p < P) {
+        const unsigned char *rec = packed + p * cbytes;
+        codes[p] = *reinterpret_cast<const unsigned *>(rec + o);
+        sb[p] = rec[so];
+      }
+    }
+    unsigned sc[PACK ? N / 4 : N] = {};
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      bool nan_block = sb[p] == 0xffu;
+      codes[p] = nan_block ? 0x7f7f7f7fu : codes[p];
+      unsigned e = nan_block ? 127u : max(sb[p], 10u);
+      if constexpr (PACK) sc[p / 4] |= e << (8 * (p % 4));
+      else sc[p] = e << 23;
+    }
+    float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+    for (int k = 0; k < 4 / COLS; ++k) {
+      float s[COLS][N];
+      if constexpr (PACK) {
+        // the unpacked scales are loop-invariant; an empty asm keeps the compiler from
+        // hoisting all N of them out of the loop, back into N registers
+#pragma unroll
+        for (int p = 0; p < N / 4; ++p) asm volatile("" : "+v"(sc[p]));
+      }
+#pragma unroll
+      for (int p = 0; p < N; ++p) {
+        unsigned scale = PACK ? (sc[p / 4] >> (8 * (p % 4)) & 0xffu) << 23 : sc[p];
+        mx8_v2f v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes[p], __uint_as_float(scale), false);
+        codes[p] >>= 8 * COLS;
+        s[0][p] = (p >= P || v.x != v.x) ? INFINITY : v.x;
+        if constexpr (COLS == 2) s[1][p] = (p >= P || v.y != v.y) ? INFINITY : v.y;
+      }
+      float r[COLS];
+#pragma unroll
+      for (int q = 0; q < COLS; ++q) {
+        sort_columns(s[q], std::make_integer_sequence<int, kMergeExchange<N>.n>{});
+        r[q] = AROUND ? mean_around_sorted(s[q], P, a, b, c, f, g) : trimmed_sorted(s[q], a, b, f);
+      }
+      // the results move down one place per new column: after the last trip y holds
+      // columns 0..3 in x..w
+      if constexpr (COLS == 2) y = make_float4(y.z, y.w, r[0], r[1]);
+      else y = make_float4(y.y, y.z, y.w, r[0]);
+    }
+    out[o / 4] = y;
+  }
+}
+
+// The checks shared by the two ops, before any launch; returns the units of the call.
+static inline int check_mx8_col(const char *op, const torch::Tensor &packed,
+                                const torch::Tensor &out) {
+  CHECK_IN(packed);
+  CHECK_IN(out);
+  TORCH_CHECK(packed.device() == out.device(), op, ": tensors must be on one device");
+  TORCH_CHECK(packed.scalar_type() == torch::kUInt8, op, ": packed data must be uint8");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat32, op, ": out must be fp32");
+  long chunk = out.numel();
+  TORCH_CHECK(chunk % 64 == 0, op, ": chunk must be a multiple of 64, got ", chunk);
+  TORCH_CHECK(chunk <= 0x40000000L, op, ": chunk ", chunk, " exceeds the 32-bit column offset");
+  TORCH_CHECK(packed.dim() == 2 && packed.size(1) == mx8_chunk_bytes(chunk), op,
+              ": packed must be (P, ", mx8_chunk_bytes(chunk), ") for chunk ", chunk);
+  long P = packed.size(0);
+  TORCH_CHECK(P >= 1 && P <= 64, op, " kernel supports 1 <= P <= 64, got ", P);
+  TORCH_CHECK((uintptr_t)packed.data_ptr() % 16 == 0 && (uintptr_t)out.data_ptr() % 16 == 0, op,
+              ": tensors must be 16-byte aligned");
+  return (int)((chunk + 255) / 256);
+}
+
+template <bool AROUND>
+static inline void launch_mx8_col(const torch::Tensor &packed, const torch::Tensor &out, int units,
+                                  int a, int b, int c, float f, float g) {
+  if (units == 0) return;  // chunk = 0: no launch
+  long P = packed.size(0), chunk = out.numel();
+  dim3 grid(n_blocks(units, NTHREADS / WAVE));
+  for_padded(P, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    launch(k_mx8_col<N, mx8_cols<N>, AROUND>, grid, 0, packed.data_ptr<uint8_t>(), (int)P, a, b, c,
+           f, g, (float4 *)out.data_ptr<float>(), (unsigned)chunk, mx8_chunk_bytes(chunk), units);
+  });
+}
+
+void mx8_column_trimmed_mean(torch::Tensor packed, long lo, long hi, torch::Tensor out) {
+  int units = check_mx8_col("mx8_column_trimmed_mean", packed, out);
+  long P = packed.size(0);
+  TORCH_CHECK(0 <= lo && lo < hi && hi <= P,
+              "mx8_column_trimmed_mean: need 0 <= lo < hi <= P, got lo=", lo, " hi=", hi, " P=", P);
+  launch_mx8_col<false>(packed, out, units, (int)lo, (int)hi, 0, (float)(hi - lo), 0.f);
+}
+
+void mx8_column_mean_around(torch::Tensor packed, long keep, long clo, long chi,
+                            torch::Tensor out) {
+  int units = check_mx8_col("mx8_column_mean_around", packed, out);
+  long P = packed.size(0);
+  TORCH_CHECK(1 <= keep && keep <= P,
+              "mx8_column_mean_around: need 1 <= keep <= P, got keep=", keep, " P=", P);
+  TORCH_CHECK(0 <= clo && clo < chi && chi <= P,
+              "mx8_column_mean_around: need 0 <= clo < chi <= P, got clo=", clo, " chi=", chi,
+              " P=", P);
+  launch_mx8_col<true>(packed, out, units, (int)keep, (int)clo, (int)chi, (float)(chi - clo),
+                       (float)keep);
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -2037,4 +2202,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sign_majority", &sign_majority);
   m.def("mx8_pack", &mx8_pack);
   m.def("mx8_unpack", &mx8_unpack);
+  m.def("mx8_column_trimmed_mean", &mx8_column_trimmed_mean);
+  m.def("mx8_column_mean_around", &mx8_column_mean_around);
 }

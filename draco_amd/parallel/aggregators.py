@@ -80,7 +80,9 @@ class Aggregator:
     # uint8 send buffer and posts its all_to_all into a (rows, world, chunk_bytes) receive
     # buffer; _exchange drains and decodes with ONE kernel into a persistent (rows * world,
     # shard) fp32 block, which collusion, mixing and every rule read as they read the fp32
-    # exchange.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
+    # exchange.  The per-coordinate rules (median, trimmed_mean, mean, meamed, phocas) with
+    # no collusion and no mixing skip that block: exchanged_packed hands them the received
+    # bytes and their kernel decodes while it loads.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
     # stays non-finite.  With one rank the rows are still packed and unpacked.  The
     # bucketed path is not built for this wire: the row ships whole from aggregate().
     wire = None
@@ -120,7 +122,7 @@ class Aggregator:
             # one rank: the packed rows are the received block
             self._recv = (torch.empty(rows, world, cb, dtype=torch.uint8, device=dev)
                           if self.comm.distributed else self._send)
-            self._recv32 = torch.empty(rows * world, shard, dtype=torch.float32, device=dev)
+            self._recv32 = None  # the decoded block: allocated by the rules that read one
         ops.mx8_pack(payload[row], self._send[row], shard)
         if self.comm.distributed:
             w = self.comm.all_to_all_row(self._send[row], self._recv[row], async_op=True)
@@ -188,6 +190,19 @@ class Aggregator:
             self.mixing(recv)
         return recv
 
+    def exchanged_packed(self, payload: torch.Tensor):
+        """On the mx8 wire with no collusion and no mixing attached: the drained exchange
+        as it travelled, (rows*world, chunk_bytes) uint8 in exchanged()'s row order, for the
+        rules whose kernel decodes it itself (ops.mx8_column_trimmed_mean /
+        ops.mx8_column_mean_around); the fp32 block is then never allocated.  None
+        otherwise (nothing is exchanged yet): the caller goes on to exchanged()."""
+        if self.wire != "mx8" or self.collusion is not None or self.mixing is not None:
+            return None
+        self._start_rest(payload)
+        self._drain()
+        # (rows, world, cb) is row l*world + src already; one rank: _recv is _send, (rows, cb)
+        return self._recv.view(payload.shape[0] * self.comm.world, -1)
+
     def _check_rows(self, P: int) -> None:
         if self.MAX_WORKERS is not None and P > self.MAX_WORKERS:
             raise ValueError(f"{self.name} supports at most {self.MAX_WORKERS} workers "
@@ -209,7 +224,11 @@ class Aggregator:
         if self.wire == "mx8":
             self._start_rest(payload)
             self._drain()
-            ops.mx8_unpack(self._recv.view(self._recv32.shape[0], -1), self._recv32)
+            P = rows * self.comm.world
+            if self._recv32 is None or self._recv32.shape[0] != P:
+                self._recv32 = torch.empty(P, self.space.shard, dtype=torch.float32,
+                                           device=payload.device)
+            ops.mx8_unpack(self._recv.view(P, -1), self._recv32)
             return self._recv32
         if not self.comm.distributed:
             return payload.view(rows, self.space.shard)
@@ -768,9 +787,14 @@ class TrimmedMeanAggregator(Aggregator):
         return self.trim, P - self.trim
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
-        recv = self.exchanged(payload)  # (P, shard)
-        lo, hi = self._bounds(recv.shape[0])
-        ops.column_trimmed_mean(recv, lo, hi, self._shard_out)
+        packed = self.exchanged_packed(payload)  # (P, chunk_bytes), or None
+        if packed is not None:
+            lo, hi = self._bounds(packed.shape[0])
+            ops.mx8_column_trimmed_mean(packed, lo, hi, self._shard_out)
+        else:
+            recv = self.exchanged(payload)  # (P, shard)
+            lo, hi = self._bounds(recv.shape[0])
+            ops.column_trimmed_mean(recv, lo, hi, self._shard_out)
         self.comm.all_gather_shard(self._shard_out, self._out)
         return self._out
 
@@ -824,9 +848,14 @@ class MeanAroundAggregator(Aggregator):
         return P - self.b, self.b, P - self.b
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
-        recv = self.exchanged(payload)  # (P, shard)
-        keep, clo, chi = self._bounds(recv.shape[0])
-        ops.column_mean_around(recv, keep, clo, chi, self._shard_out)
+        packed = self.exchanged_packed(payload)  # (P, chunk_bytes), or None
+        if packed is not None:
+            keep, clo, chi = self._bounds(packed.shape[0])
+            ops.mx8_column_mean_around(packed, keep, clo, chi, self._shard_out)
+        else:
+            recv = self.exchanged(payload)  # (P, shard)
+            keep, clo, chi = self._bounds(recv.shape[0])
+            ops.column_mean_around(recv, keep, clo, chi, self._shard_out)
         self.comm.all_gather_shard(self._shard_out, self._out)
         return self._out
 
@@ -1121,7 +1150,7 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
     if name is not None:
         agg.name = name
     if mx8:
-        agg.wire = "mx8"  # see Aggregator.wire: every rule reads the decoded block
+        agg.wire = "mx8"  # see Aggregator.wire: the decoded block, or exchanged_packed
     if nnm:
         from .mixing import NearestNeighborMixing  # mixing imports this module
 

@@ -526,6 +526,19 @@ def sign_majority_compare(rounds=3):
         print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def ev_ms(fn, iters, warmup):
+    """ms per call: events around `iters` back-to-back launches after a warm-up"""
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
 def mx8_compare(rounds=3):
     """The MXFP8 wire: mx8_pack on one 11.2M-element row (4 B read + 1.03 B written per
     element) and mx8_unpack on the packed 24 x 11.2M and 64 x 11.2M blocks (1.03 B read +
@@ -539,17 +552,6 @@ def mx8_compare(rounds=3):
     d = 11_173_952
     d = (d + 63) // 64 * 64
     cb = ops.mx8_chunk_bytes(d)
-
-    def ev_ms(fn, iters, warmup):
-        for _ in range(warmup):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / iters
 
     times, order = {}, []
     for rows in (24, 64):
@@ -593,6 +595,60 @@ def mx8_compare(rounds=3):
                 times[name].append(ms)
                 report(name, ms, nbytes)
         del x, packed, out, h
+    print("# min - max over rounds, GB/s at the min")
+    for name, nbytes in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
+
+
+def mx8_fused_compare(rounds=3):
+    """The rules that decode the MXFP8 records in their own kernel (ops.mx8_column_trimmed_mean
+    / ops.mx8_column_mean_around) beside the two-launch route they replace (mx8_unpack into a
+    (P, d) fp32 block, then the fp32 column op), on packed 24 x 11.2M and 64 x 11.2M blocks of
+    distinct rows: trimmed mean b=1, median, meamed b=1; mx8_unpack alone is the floor of the
+    two-launch route.  Each arm's GB/s counts its own bytes (fused: the records + the output;
+    two launches: the records, the block written and read back, the output); the time is the
+    comparison.  Outputs are compared once before timing (NaN as NaN, values ==); event
+    timing, the arms alternate inside each round; min-max over the rounds per arm."""
+    d = (11_173_952 + 63) // 64 * 64
+    cb = ops.mx8_chunk_bytes(d)
+    times, order = {}, []
+    for P in (24, 64):
+        packed = torch.empty(P, cb, dtype=torch.uint8, device=DEV)
+        for p in range(P):
+            x = torch.randn(d, device=DEV) * 1e-2
+            x[p::1001] = float("nan")
+            ops.mx8_pack(x, packed[p], d)
+        del x
+        block = torch.empty(P, d, device=DEV)
+        out, ref = torch.empty(d, device=DEV), torch.empty(d, device=DEV)
+        med = ((P - 1) // 2, P // 2 + 1)
+        rules = [("trimmed mean b=1", ops.mx8_column_trimmed_mean, ops.column_trimmed_mean, (1, P - 1)),
+                 ("median", ops.mx8_column_trimmed_mean, ops.column_trimmed_mean, med),
+                 ("meamed b=1", ops.mx8_column_mean_around, ops.column_mean_around, (P - 1, *med))]
+        arms = [(f"mx8_unpack ({P} x 11.2M)", lambda: ops.mx8_unpack(packed, block), P * (cb + 4 * d))]
+        for name, fused, plain, args in rules:
+            def one(fused=fused, args=args):
+                fused(packed, *args, out)
+
+            def two(plain=plain, args=args):
+                ops.mx8_unpack(packed, block)
+                plain(block, *args, ref)
+            one(), two()
+            nan = torch.isnan(ref)
+            assert bool((torch.isnan(out) == nan).all()) and bool((out[~nan] == ref[~nan]).all()), name
+            arms += [(f"fused {name} ({P} x 11.2M)", one, P * cb + 4 * d),
+                     (f"unpack + {name} ({P} x 11.2M)", two, P * (cb + 8 * d) + 4 * d)]
+        for r in range(rounds):
+            print(f"# round {r}")
+            for name, fn, nbytes in arms:
+                ms = ev_ms(fn, iters=50, warmup=10)
+                if name not in times:
+                    times[name] = []
+                    order.append((name, nbytes))
+                times[name].append(ms)
+                report(name, ms, nbytes)
+        del packed, block, out, ref
     print("# min - max over rounds, GB/s at the min")
     for name, nbytes in order:
         lo, hi = min(times[name]), max(times[name])
@@ -734,6 +790,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("SIGN_ONLY") == "1":
         sign_majority_compare()
+        raise SystemExit(0)
+    if os.environ.get("MX8_FUSED_ONLY") == "1":
+        mx8_fused_compare()
         raise SystemExit(0)
     if os.environ.get("MX8_ONLY") == "1":
         mx8_compare()
