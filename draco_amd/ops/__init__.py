@@ -26,6 +26,8 @@ __all__ = [
     "mx8_chunk_bytes",
     "mx8_column_trimmed_mean",
     "mx8_column_mean_around",
+    "mx8_segment_gram",
+    "mx8_segment_mean_around",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -234,6 +236,34 @@ def mx8_column_mean_around(packed, keep, clo, chi, out):
         ext.mx8_column_mean_around(packed, int(keep), int(clo), int(chi), out)
         return
     fallback.mx8_column_mean_around(packed, int(keep), int(clo), int(chi), out)
+
+
+def mx8_segment_gram(packed, seg):
+    """(L, P, P) fp32 = segment_gram(mx8_unpack(packed), seg) for packed (P,
+    mx8_chunk_bytes(chunk)) uint8, 1 <= P <= 32, chunk % 64 == 0; seg: (L+1,) local bounds,
+    never read on the host.  On the GPU the block-scaled FP8 matrix instruction multiplies the
+    records themselves (a lane holds one MX block of one row as both operands): products are
+    exact, the fp32 sums are added with float atomics (last bits may differ between runs), the
+    result is exactly symmetric and non-finite wherever the definition's is.  Definition and
+    checks: fallback.mx8_segment_gram."""
+    ext = _native_for(packed)
+    if ext is not None:
+        return ext.mx8_segment_gram(packed, seg.to(packed.device))
+    return fallback.mx8_segment_gram(packed, seg)
+
+
+def mx8_segment_mean_around(packed, sel, seg, keep, clo, chi, out):
+    """out (chunk,) fp32 = segment_mean_around(mx8_unpack(packed), sel, seg, keep, clo, chi),
+    bit for bit, for packed (P, mx8_chunk_bytes(chunk)) uint8 and sel (L, T), 1 <= T <= P <= 32.
+    On the GPU one kernel gathers a dword of codes (four columns) per selected row from the
+    records; unselected rows are never read.  Definition and checks:
+    fallback.mx8_segment_mean_around."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx8_segment_mean_around(packed, sel.to(packed.device), seg.to(packed.device),
+                                    int(keep), int(clo), int(chi), out)
+        return
+    fallback.mx8_segment_mean_around(packed, sel, seg, int(keep), int(clo), int(chi), out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

@@ -19,6 +19,8 @@
 // k_mx8_pack / k_mx8_unpack (the MXFP8 block-scaled wire) convert with the gfx950 scaled
 // FP8 instructions; the block scale is reduced across eight lanes by DPP.  k_mx8_col is
 // the column sort on that wire: it reads the packed records, four columns per lane.
+// k_mx8_seg_gram / k_mx8_seg_mean_around are Multi-Krum's and Bulyan's two steps on it: the
+// Gram decodes a lane's MX block in registers and multiplies on the matrix unit.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -2168,6 +2170,348 @@ void mx8_column_mean_around(torch::Tensor packed, long keep, long clo, long chi,
                        (float)keep);
 }
 
+// --------------------------------------------------------------------------- mx8 krum rules
+// Multi-Krum and Bulyan on the mx8 wire: mx8_segment_gram = segment_gram(mx8_unpack(.)) and
+// mx8_segment_mean_around = segment_mean_around(mx8_unpack(.), ..), both from the packed
+// records; the fp32 (P, chunk) block is never formed.
+//
+// k_mx8_seg_gram.  Lane (h = lane / 32, q = lane % 32) holds ONE MX BLOCK OF ONE ROW: row q,
+// block 2j + h of the 64-column span j, 32 code bytes in 8 registers loaded as two 16-byte
+// accesses, plus the block's scale byte; rows >= P are zero codes and are never loaded.  The
+// block is decoded in registers (16 v_cvt_scalef32_pk_f32_fp8, as k_mx8_unpack does) and
+// multiplied with v_mfma_f32_32x32x2_f32, the instruction of k_mix_rows: step s takes float s
+// of every lane, i.e. K = columns s and 32 + s of the span.  A Gram is A A^T and the A and B
+// operands have the same lane layout, so the same register is both operands; no LDS for the
+// operands.  With P <= 32 the 32 x 32 accumulator tile (16 registers) is a whole Gram.
+//
+// Why not the block-scaled FP8 instruction.  v_mfma_scale_f32_32x32x64_f8f6f4 was built first
+// and measured on the MI355X.  Its layout: lane (h, q) supplies row q, registers 0..3 = 16
+// codes of K block 0, registers 4..7 = 16 codes of K block 1 (both at K offset 16h), scale
+// operand = the scale of block h; with that the per-block sums of squares agreed with fp64 to
+// a factor 0.99997 .. 0.999999, always below 1: the instruction truncates the aligned
+// products well above fp32's last bit (2e-5 relative against the 4e-6 that 32 fp32 additions
+// may lose), and missed the bound len * 2^-23 * sum|x_a||x_b| of tests/test_mx8_gram_gpu.py
+// by 3x at len = 67.  The fp32 instruction on exactly decoded values meets it.
+//
+// Work split.  The spans that meet [seg[0], seg[L]) are cut into one contiguous share per
+// wave; a wave walks its share MX8_GRAM_TRIP spans per trip, all loads of a trip issued before
+// the first multiply, and the accumulator stays in place for as long as the spans belong to
+// one segment.  The bounds are staged in LDS (segment_lds / stage_segments): no host copy, no
+// descriptor table.  Everything about segments is wave-uniform: a span inside the current
+// segment is decoded as loaded; a span that meets a bound is multiplied once per
+// piece [lo, hi), with the codes outside the piece set to 0x00 (a bound falls anywhere: inside
+// a span, a block, a dword); when the segment changes the tile is flushed and zeroed.
+//
+// The format's rules are applied in registers, the instruction's own treatment of special
+// inputs is not relied on.  The scale byte is clamped to >= 10 before the convert.
+// What decodes to a non-finite value makes the row non-finite for its segment: a NaN code
+// (0x7F / 0xFF), a 0xFF scale on a block with a column in the piece, and a product code x
+// scale that overflows fp32 (exponent field + scale byte >= 262: only scale bytes >= 247 can).
+// All three are byte-parallel integer tests on the masked codes; the wave keeps the 32-bit set
+// of such rows, and the flush writes NaN to every entry of their rows and columns, exactly
+// the entries that the definition makes non-finite through them (Inf x 0 = NaN, Inf x y =
+// +-Inf).  Whatever the instruction computes from those inputs lands in those entries only.
+//
+// Output.  Float atomics, not a fixed-order reduction: a wave adds the upper triangle of its
+// tile to out[l] (the lower one is the same number, formed from the same products), and
+// k_gram_mirror, launched behind it, copies the upper triangle over the lower: exactly
+// symmetric, zero where no column contributes, the sum order (and so the last bits) may
+// differ between two runs as for k_seg_gram.  ~1.3 flushes per wave against one per 256
+// columns there.
+#define MX8_GRAM_TRIP 4
+typedef int mx8_v8i __attribute__((ext_vector_type(8)));
+
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_seg_gram(const unsigned char *__restrict__ packed, const long *__restrict__ seg, int L, int P,
+               float *__restrict__ out /* (L, P, P), zeroed */, long chunk, long cbytes) {
+  extern __shared__ long s_seg[];
+  stage_segments(s_seg, seg, L);
+  __syncthreads();
+  const int lane = threadIdx.x % WAVE, h = lane / 32, q = lane % 32;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const long first = min(max(s_seg[0], 0L), chunk), last = min(max(s_seg[L], 0L), chunk);
+  const long sp0 = first / 64, sp1 = (last + 63) / 64;  // the spans that meet a segment
+  if (sp1 <= sp0) return;
+  const long nw = gridDim.x * (long)(NTHREADS / WAVE);
+  const long per = (sp1 - sp0 + nw - 1) / nw;
+  const long a = sp0 + (blockIdx.x * (long)(NTHREADS / WAVE) + wave) * per;
+  const long b = min(a + per, sp1);
+  const unsigned char *rec = packed + q * cbytes;  // read behind q < P only
+  acc16 acc = 0.f;
+  int cur_l = -1;     // the segment the tile belongs to
+  unsigned bad = 0u;  // its rows with a non-finite element
+
+  auto flush = [&]() __attribute__((always_inline)) {
+    float *base = out + (long)cur_l * P * P;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      int i = 8 * (v / 4) + 4 * h + v % 4;  // the tile's row in register v; its column is q
+      if (i <= q && q < P)
+        atomicAdd(&base[i * P + q], ((bad >> i | bad >> q) & 1u) ? __uint_as_float(0x7fc00000u) : acc[v]);
+    }
+    acc = 0.f;
+    bad = 0u;
+  };
+
+  // one span: its pieces, 32 multiply steps each (a lambda called once per span of the trip and not
+  // a loop over them: the loop is not unrolled around the ballot, and codes[] must stay in
+  // registers)
+  auto span = [&](const mx8_v8i &codes_t, unsigned sb_t, long spn) __attribute__((always_inline)) {
+    const long c0 = spn * 64;
+    const long end = spn < b ? min(c0 + 64, last) : 0;  // no such span: no piece
+    long cur = max(c0, first);
+    // overflow: exponent field + scale byte >= 262, i.e. field + k >= 16 with k = byte - 246
+    const unsigned k = (max(sb_t, 246u) - 246u) * 0x01010101u;
+    const float scale = __uint_as_float((sb_t == 0xffu ? 127u : max(sb_t, 10u)) << 23);
+    while (cur < end) {
+      int l = cur_l;
+      if (l < 0 || cur < s_seg[l] || cur >= s_seg[l + 1]) l = find_segment(s_seg, L, cur);
+      if (l != cur_l) {
+        if (cur_l >= 0) flush();
+        cur_l = l;
+      }
+      const long hi = min(s_seg[l + 1], end);
+      if (hi <= cur) break;  // bounds that do not ascend: nothing to add
+      mx8_v8i c = codes_t;
+      // the lane's block is columns [c0 + 32 h, + 32); [s, e) of it lies in the piece
+      const int s = (int)min(max(cur - c0 - 32 * h, 0L), 32L);
+      const int e = (int)min(max(hi - c0 - 32 * h, 0L), 32L);
+      if (cur > c0 || hi < c0 + 64) {
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+          int s0 = min(max(s - 4 * d, 0), 4), e0 = min(max(e - 4 * d, 0), 4);
+          unsigned m = s0 < e0 ? (0xffffffffu >> (8 * (4 - e0))) & (0xffffffffu << (8 * s0)) : 0u;
+          c[d] &= (int)m;
+        }
+      }
+      unsigned nf = (sb_t == 0xffu && s < e) ? 1u : 0u;  // a NaN block with a column here
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {
+        unsigned x = (unsigned)c[d];
+        nf |= ((x & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u;  // a NaN code
+        nf |= (((x >> 3) & 0x0f0f0f0fu) + k) & 0x10101010u;     // code x scale overflows
+      }
+      unsigned long long rows = __ballot(nf != 0u);
+      bad |= (unsigned)rows | (unsigned)(rows >> 32);
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {
+        mx8_v2f lo2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c[d], scale, false);
+        mx8_v2f hi2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c[d], scale, true);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lo2.x, lo2.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lo2.y, lo2.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hi2.x, hi2.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hi2.y, hi2.y, acc, 0, 0, 0);
+      }
+      cur = hi;
+    }
+  };
+
+  for (long sp = a; sp < b; sp += MX8_GRAM_TRIP) {  // wave-uniform
+    mx8_v8i codes[MX8_GRAM_TRIP];
+    unsigned sb[MX8_GRAM_TRIP];
+#pragma unroll
+    for (int t = 0; t < MX8_GRAM_TRIP; ++t) {
+      codes[t] = 0;
+      sb[t] = 127u;
+      if (sp + t < b && q < P) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(rec + (sp + t) * 64 + 32 * h);
+        uint4 lo = src[0], hi = src[1];
+        codes[t] = mx8_v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w,
+                           (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+        sb[t] = rec[chunk + (sp + t) * 2 + h];
+      }
+    }
+    static_assert(MX8_GRAM_TRIP == 4, "one call per span of the trip");
+    span(codes[0], sb[0], sp);
+    span(codes[1], sb[1], sp + 1);
+    span(codes[2], sb[2], sp + 2);
+    span(codes[3], sb[3], sp + 3);
+  }
+  if (cur_l >= 0) flush();
+}
+
+__global__ void k_gram_mirror(float *__restrict__ out, int P, long n /* L * P * P */) {
+  long gstride = gridDim.x * (long)blockDim.x;
+  for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < n; t += gstride) {
+    int r = (int)(t % (P * P)), i = r / P, j = r % P;
+    if (j < i) out[t] = out[t - r + j * P + i];
+  }
+}
+
+// the chunk whose record has `cbytes` bytes (mx8_chunk_bytes is increasing in chunk)
+static inline long mx8_chunk_of(const char *op, long cbytes) {
+  for (long c = std::max(0L, cbytes * 32 / 33 / 64 * 64 - 64); mx8_chunk_bytes(c) <= cbytes; c += 64)
+    if (mx8_chunk_bytes(c) == cbytes) return c;
+  TORCH_CHECK(false, op, ": ", cbytes, " bytes are no mx8 record of a chunk that is a multiple of 64");
+  return 0;
+}
+
+torch::Tensor mx8_segment_gram(torch::Tensor packed, torch::Tensor seg) {
+  const char *op = "mx8_segment_gram";
+  CHECK_IN(packed);
+  TORCH_CHECK(packed.scalar_type() == torch::kUInt8, op, ": packed data must be uint8");
+  TORCH_CHECK(packed.dim() == 2, op, ": packed must be (P, chunk_bytes)");
+  SegmentLds sl = segment_lds(op, seg, 0);
+  TORCH_CHECK(seg.device() == packed.device(), op, ": tensors must be on one device");
+  long P = packed.size(0), chunk = mx8_chunk_of(op, packed.size(1));
+  TORCH_CHECK(P >= 1 && P <= 32, op, " kernel supports 1 <= P <= 32 (one 32x32 matrix tile), got ", P);
+  TORCH_CHECK((uintptr_t)packed.data_ptr() % 16 == 0, op, ": packed must be 16-byte aligned");
+  auto out = torch::zeros({(long)sl.L, P, P}, torch::dtype(torch::kFloat32).device(packed.device()));
+  if (sl.L == 0 || chunk == 0) return out;
+  long trips = (chunk / 64 + MX8_GRAM_TRIP - 1) / MX8_GRAM_TRIP;
+  launch(k_mx8_seg_gram, dim3(n_blocks(trips, NTHREADS / WAVE)), sl.bytes, packed.data_ptr<uint8_t>(),
+         seg.data_ptr<long>(), sl.L, (int)P, out.data_ptr<float>(), chunk, mx8_chunk_bytes(chunk));
+  launch(k_gram_mirror, dim3(n_blocks(out.numel(), NTHREADS)), 0, out.data_ptr<float>(), (int)P,
+         out.numel());
+  return out;
+}
+
+// k_mx8_seg_mean_around: k_seg_mean_around's per-segment gather with k_mx8_col's access
+// pattern.  A wave walks units of 256 columns; a lane owns the four adjacent columns of one
+// dword of codes and stores one float4.  The bounds are staged in LDS, the (L, T) table is
+// read from global memory, indices are clamped into [0, P), and an unselected row is never
+// read, all as in k_seg_mean_around.
+//
+// Whole dwords.  When every lane of the wave has its four columns in ONE segment (or all four
+// outside [seg[0], seg[L])), a lane reads per selected row one dword of codes and the block's
+// scale byte (branch-free over the padded slots, which re-read entry T-1), folds a NaN block
+// into the codes and then runs k_mx8_col's loop: one scaled convert gives two columns, both
+// are sorted (sort_columns) and reduced (mean_around_sorted), the codes shift down 16 bits
+// and the loop, which is not unrolled, runs once more.  T <= 32, so two columns fit.
+//
+// Per column.  A wave in which some dword straddles a bound takes every lane through the same
+// loop one column at a time: the column's own segment, a byte of codes per selected row, one
+// sort.  That is at most one wave per bound and need not be fast.
+//
+// Both give segment_mean_around's bits: NaN (a NaN code or a 0xFF scale) -> +inf, slots >= T
+// +inf, the same network and window arithmetic.  Columns outside the segments get +0.0 and
+// every element of out is written.
+template <int N>
+__device__ __forceinline__ float4 mx8_gather_dwords(const unsigned char *__restrict__ packed,
+                                                    const long *__restrict__ row, int T, int P,
+                                                    long cbytes, unsigned o, unsigned so, int keep,
+                                                    int clo, int chi, float ccnt, float kcnt) {
+  unsigned codes[N], sc[N];
+#pragma unroll
+  for (int p = 0; p < N; ++p) {
+    long r = row[p < T ? p : T - 1];
+    r = r < 0 ? 0 : (r >= P ? (long)P - 1 : r);
+    const unsigned char *rec = packed + r * cbytes;
+    codes[p] = *reinterpret_cast<const unsigned *>(rec + o);
+    sc[p] = rec[so];
+  }
+#pragma unroll
+  for (int p = 0; p < N; ++p) {
+    bool nan_block = sc[p] == 0xffu;
+    codes[p] = nan_block ? 0x7f7f7f7fu : codes[p];
+    sc[p] = (nan_block ? 127u : max(sc[p], 10u)) << 23;
+  }
+  float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+  for (int k = 0; k < 2; ++k) {
+    float s[2][N];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      mx8_v2f v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes[p], __uint_as_float(sc[p]), false);
+      codes[p] >>= 16;
+      s[0][p] = (p >= T || v.x != v.x) ? INFINITY : v.x;
+      s[1][p] = (p >= T || v.y != v.y) ? INFINITY : v.y;
+    }
+    float r[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      sort_columns(s[c], std::make_integer_sequence<int, kMergeExchange<N>.n>{});
+      r[c] = mean_around_sorted(s[c], T, keep, clo, chi, ccnt, kcnt);
+    }
+    y = make_float4(y.z, y.w, r[0], r[1]);
+  }
+  return y;
+}
+
+template <int N>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_seg_mean_around(const unsigned char *__restrict__ packed, const long *__restrict__ sel,
+                      const long *__restrict__ seg, int L, int T, int P, int keep, int clo, int chi,
+                      float ccnt, float kcnt, float4 *__restrict__ out, unsigned chunk, long cbytes,
+                      int units) {
+  extern __shared__ long s_seg[];
+  stage_segments(s_seg, seg, L);
+  __syncthreads();
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const int ustride = gridDim.x * (NTHREADS / WAVE);
+  for (int u = blockIdx.x * (NTHREADS / WAVE) + wave; u < units; u += ustride) {
+    const unsigned o = (unsigned)u * 256u + 4u * lane;  // the lane's first column
+    const bool inb = o < chunk;  // chunk % 64 == 0: four columns are inside or outside together
+    const bool v0 = inb && in_segments(s_seg, L, o);
+    const int l0 = v0 ? find_segment(s_seg, L, o) : 0;
+    const bool same = v0 && (long)o + 3 < s_seg[l0 + 1];
+    const bool none = !inb || (long)o + 3 < s_seg[0] || (long)o >= s_seg[L];
+    float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (__all(same || none)) {
+      if (same)
+        y = mx8_gather_dwords<N>(packed, sel + (long)l0 * T, T, P, cbytes, o, chunk + o / 32, keep,
+                                 clo, chi, ccnt, kcnt);
+    } else {
+#pragma unroll 1
+      for (int k = 0; k < 4; ++k) {
+        const unsigned col = o + k;
+        const bool valid = inb && in_segments(s_seg, L, col);
+        float s[N];
+#pragma unroll
+        for (int p = 0; p < N; ++p) s[p] = INFINITY;
+        if (valid) {
+          const long *row = sel + (long)find_segment(s_seg, L, col) * T;
+#pragma unroll
+          for (int p = 0; p < N; ++p) {
+            long r = row[p < T ? p : T - 1];
+            r = r < 0 ? 0 : (r >= P ? (long)P - 1 : r);
+            const unsigned char *rec = packed + r * cbytes;
+            unsigned code = rec[col], sbyte = rec[chunk + col / 32];
+            bool nan_block = sbyte == 0xffu;
+            float scale = __uint_as_float((nan_block ? 127u : max(sbyte, 10u)) << 23);
+            mx8_v2f v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(nan_block ? 0x7fu : code, scale, false);
+            s[p] = (p < T && v.x == v.x) ? v.x : INFINITY;
+          }
+        }
+        sort_columns(s, std::make_integer_sequence<int, kMergeExchange<N>.n>{});
+        float r = mean_around_sorted(s, T, keep, clo, chi, ccnt, kcnt);
+        y = make_float4(y.y, y.z, y.w, valid ? r : 0.f);
+      }
+    }
+    if (inb) out[o / 4] = y;
+  }
+}
+
+void mx8_segment_mean_around(torch::Tensor packed, torch::Tensor sel, torch::Tensor seg, long keep,
+                             long clo, long chi, torch::Tensor out) {
+  const char *op = "mx8_segment_mean_around";
+  int units = check_mx8_col(op, packed, out);
+  CHECK_IDX(sel);
+  TORCH_CHECK(sel.dim() == 2, op, ": sel must be 2D (L, T)");
+  SegmentLds sl = segment_lds(op, seg, 0);
+  TORCH_CHECK(sel.device() == packed.device() && seg.device() == packed.device(), op,
+              ": tensors must be on one device");
+  long P = packed.size(0), T = sel.size(1), chunk = out.numel();
+  TORCH_CHECK(P <= 32, op, " kernel supports 1 <= P <= 32, got ", P);
+  TORCH_CHECK(sel.size(0) == sl.L, op, ": sel must have one row per segment, got ", sel.size(0),
+              " rows for L=", sl.L);
+  TORCH_CHECK(T >= 1 && T <= P, op, ": need 1 <= T <= P, got T=", T, " P=", P);
+  TORCH_CHECK(1 <= keep && keep <= T, op, ": need 1 <= keep <= T, got keep=", keep, " T=", T);
+  TORCH_CHECK(0 <= clo && clo < chi && chi <= T, op, ": need 0 <= clo < chi <= T, got clo=", clo,
+              " chi=", chi, " T=", T);
+  if (units == 0) return;  // chunk = 0: no launch
+  dim3 grid(n_blocks(units, NTHREADS / WAVE));
+  for_padded(T, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N <= 32)  // T <= P <= 32
+      launch(k_mx8_seg_mean_around<N>, grid, sl.bytes, packed.data_ptr<uint8_t>(),
+             sel.data_ptr<long>(), seg.data_ptr<long>(), sl.L, (int)T, (int)P, (int)keep, (int)clo,
+             (int)chi, (float)(chi - clo), (float)keep, (float4 *)out.data_ptr<float>(),
+             (unsigned)chunk, mx8_chunk_bytes(chunk), units);
+  });
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -2204,4 +2548,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx8_unpack", &mx8_unpack);
   m.def("mx8_column_trimmed_mean", &mx8_column_trimmed_mean);
   m.def("mx8_column_mean_around", &mx8_column_mean_around);
+  m.def("mx8_segment_gram", &mx8_segment_gram);
+  m.def("mx8_segment_mean_around", &mx8_segment_mean_around);
 }

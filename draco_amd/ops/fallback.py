@@ -821,6 +821,49 @@ def segment_mean_around(x: torch.Tensor, sel: torch.Tensor, seg: torch.Tensor, k
             column_mean_around(x[rows[l]][:, lo:hi], keep, clo, chi, out[lo:hi])
 
 
+# --------------------------------------------------------------------- mx8 krum rules
+def _mx8_chunk_of(op: str, cbytes: int) -> int:
+    """The chunk whose packed record has `cbytes` bytes (mx8_chunk_bytes is increasing)."""
+    c = max(0, cbytes * 32 // 33 // 64 * 64 - 64)
+    while mx8_chunk_bytes(c) < cbytes:
+        c += 64
+    if mx8_chunk_bytes(c) != cbytes:
+        raise ValueError(f"{op}: {cbytes} bytes are no mx8 record of a chunk that is a "
+                         f"multiple of 64")
+    return c
+
+
+def _check_krum_rows(op: str, packed: torch.Tensor) -> None:
+    if packed.dim() != 2 or not 1 <= packed.shape[0] <= 32:
+        raise ValueError(f"{op} supports packed (P, chunk_bytes) with 1 <= P <= 32, got "
+                         f"{tuple(packed.shape)}")
+
+
+@torch.no_grad()
+def mx8_segment_gram(packed: torch.Tensor, seg: torch.Tensor) -> torch.Tensor:
+    """(L, P, P) fp32 = segment_gram of the decoded rows of packed (P, mx8_chunk_bytes(chunk))
+    uint8, 1 <= P <= 32 (one 32x32 matrix tile in the HIP kernel): by definition mx8_unpack
+    into a temporary, then segment_gram.  The HIP kernel multiplies the records themselves
+    with the block-scaled FP8 matrix instruction: every product is exact, only the fp32
+    accumulation order differs, and an entry that is non-finite here is non-finite there."""
+    _check_krum_rows("mx8_segment_gram", packed)
+    chunk = _mx8_chunk_of("mx8_segment_gram", packed.shape[1])
+    x = torch.empty(packed.shape[0], chunk, dtype=torch.float32, device=packed.device)
+    mx8_unpack(packed, x)
+    return segment_gram(x, seg)
+
+
+@torch.no_grad()
+def mx8_segment_mean_around(packed: torch.Tensor, sel: torch.Tensor, seg: torch.Tensor,
+                            keep: int, clo: int, chi: int, out: torch.Tensor) -> None:
+    """out (chunk,) = segment_mean_around of the decoded rows of packed, 1 <= T <= P <= 32: by
+    definition mx8_unpack into a temporary, then segment_mean_around.  The HIP kernel gives
+    the same bits from the packed bytes."""
+    _check_krum_rows("mx8_segment_mean_around", packed)
+    x = _mx8_decoded("mx8_segment_mean_around", packed, out)
+    segment_mean_around(x, sel, seg, keep, clo, chi, out.view(-1))
+
+
 # --------------------------------------------------------------------- dtype cast
 @torch.no_grad()
 def cast_to_bf16(x: torch.Tensor, out: torch.Tensor) -> None:

@@ -80,9 +80,10 @@ class Aggregator:
     # uint8 send buffer and posts its all_to_all into a (rows, world, chunk_bytes) receive
     # buffer; _exchange drains and decodes with ONE kernel into a persistent (rows * world,
     # shard) fp32 block, which collusion, mixing and every rule read as they read the fp32
-    # exchange.  The per-coordinate rules (median, trimmed_mean, mean, meamed, phocas) with
+    # exchange.  The per-coordinate rules (median, trimmed_mean, mean, meamed, phocas) and
+    # multi_krum / bulyan with
     # no collusion and no mixing skip that block: exchanged_packed hands them the received
-    # bytes and their kernel decodes while it loads.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
+    # bytes and their kernels decode while they load.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
     # stays non-finite.  With one rank the rows are still packed and unpacked.  The
     # bucketed path is not built for this wire: the row ships whole from aggregate().
     wire = None
@@ -194,7 +195,8 @@ class Aggregator:
         """On the mx8 wire with no collusion and no mixing attached: the drained exchange
         as it travelled, (rows*world, chunk_bytes) uint8 in exchanged()'s row order, for the
         rules whose kernel decodes it itself (ops.mx8_column_trimmed_mean /
-        ops.mx8_column_mean_around); the fp32 block is then never allocated.  None
+        ops.mx8_column_mean_around, ops.mx8_segment_gram / ops.mx8_segment_mean_around); the
+        fp32 block is then never allocated.  None
         otherwise (nothing is exchanged yet): the caller goes on to exchanged()."""
         if self.wire != "mx8" or self.collusion is not None or self.mixing is not None:
             return None
@@ -636,7 +638,9 @@ class _KrumSelectAggregator(Aggregator):
     local shard, ONE (L, P, P) allreduce, on-device selection of T rows per segment
     (no host read), ONE kernel (ops.segment_mean_around gathers each column's rows
     through the per-segment index table), all_gather.  last_sel keeps the (L, T)
-    selection of the latest call, on device."""
+    selection of the latest call, on device.  On the mx8 wire with no collusion and no
+    mixing, ops.mx8_segment_gram and ops.mx8_segment_mean_around do both steps on the
+    received records and the fp32 block is never allocated."""
 
     MAX_WORKERS = KrumAggregator.MAX_WORKERS
     MAX_WORKERS_WHY = KrumAggregator.MAX_WORKERS_WHY
@@ -660,14 +664,20 @@ class _KrumSelectAggregator(Aggregator):
                 f"{self.name} with f={self.f} needs at least {why} = {need} workers, got {P}")
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
-        recv = self.exchanged(payload)  # (P, shard)
+        packed = self.exchanged_packed(payload)  # (P, chunk_bytes), or None
+        if packed is not None:
+            # both kernels read the received records; no fp32 block
+            recv, gram_op, decode_op = packed, ops.mx8_segment_gram, ops.mx8_segment_mean_around
+        else:
+            recv = self.exchanged(payload)  # (P, shard)
+            gram_op, decode_op = ops.segment_gram, ops.segment_mean_around
         select, keep, clo, chi = self._plan(recv.shape[0])
-        gram = ops.segment_gram(recv, self.local_seg)  # (L, P, P)
+        gram = gram_op(recv, self.local_seg)  # (L, P, P)
         self.comm.all_reduce(gram)
         sel = select(gram)  # (L, T)
         self.last_sel = sel
         # writes the whole shard, the zero pad tail past the last segment included
-        ops.segment_mean_around(recv, sel, self.local_seg, keep, clo, chi, self._shard_out)
+        decode_op(recv, sel, self.local_seg, keep, clo, chi, self._shard_out)
         self.comm.all_gather_shard(self._shard_out, self._out)
         return self._out
 

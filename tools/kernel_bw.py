@@ -655,6 +655,78 @@ def mx8_fused_compare(rounds=3):
         print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
 
 
+def mx8_gram_compare(rounds=3):
+    """Multi-Krum / Bulyan on the mx8 wire: ops.mx8_segment_gram and ops.mx8_segment_mean_around
+    on the packed 24 x 11.2M records beside the route they replace (mx8_unpack into a (P, d)
+    fp32 block, then segment_gram and segment_mean_around on it), over ResNet-18's own 62
+    parameter tensors as segments, at Bulyan's plans for (P=24, f=1) and (P=23, f=5).  The
+    gather outputs are compared first (NaN as NaN, values ==); both Grams are compared with
+    the fp64 Gram of the decoded rows and the largest |G - G64| / (len * 2^-23 * S),
+    S = sum |x_a||x_b|, is printed for each.  Event timing, the arms alternate inside each
+    round; min-max over the rounds per arm."""
+    from draco_amd.models import build_model
+    sizes = [p.numel() for p in build_model("ResNet18", "Cifar10").parameters()]
+    seg_host = [0]
+    for n in sizes:
+        seg_host.append(seg_host[-1] + n)
+    d = (seg_host[-1] + 63) // 64 * 64
+    seg = torch.tensor(seg_host, dtype=torch.int64, device=DEV)
+    cb = ops.mx8_chunk_bytes(d)
+    gen = torch.Generator().manual_seed(0)
+    out, ref = torch.empty(d, device=DEV), torch.empty(d, device=DEV)
+    times, order, arms = {}, [], []
+    print(f"# d = {d}, {len(sizes)} segments, lengths {min(sizes)} .. {max(sizes)}")
+    for P, f in ((24, 1), (23, 5)):
+        T = P - 2 * f
+        plan = (T - 2 * f, (T - 1) // 2, T // 2 + 1)
+        packed = torch.empty(P, cb, dtype=torch.uint8, device=DEV)
+        for p in range(P):
+            x = torch.zeros(d, device=DEV)
+            x[:seg_host[-1]] = torch.randn(seg_host[-1], device=DEV) * 1e-2
+            ops.mx8_pack(x, packed[p], d)
+        del x
+        block = torch.empty(P, d, device=DEV)
+        sel = torch.stack([torch.randperm(P, generator=gen)[:T] for _ in sizes]).to(DEV)
+        ops.mx8_unpack(packed, block)
+        ops.segment_mean_around(block, sel, seg, *plan, ref)
+        ops.mx8_segment_mean_around(packed, sel, seg, *plan, out)
+        assert bool((out == ref).all()), (P, f, "gather on the records != gather on the block")
+        g_new, g_old = ops.mx8_segment_gram(packed, seg).double(), ops.segment_gram(block, seg).double()
+        worst = {"mx8_segment_gram": 0.0, "segment_gram": 0.0}
+        for l, (lo, hi) in enumerate(zip(seg_host[:-1], seg_host[1:])):
+            x64 = block[:, lo:hi].double()
+            bound = (hi - lo) * 2.0 ** -23 * (x64.abs() @ x64.abs().T)
+            for name, g in (("mx8_segment_gram", g_new), ("segment_gram", g_old)):
+                worst[name] = max(worst[name], float(((g[l] - x64 @ x64.T).abs() / bound).max()))
+        del x64, bound
+        assert bool((g_new == g_new.transpose(1, 2)).all())
+        for name, w in worst.items():
+            print(f"# P={P}: max |G - G64| / (len * 2^-23 * S), {name}: {w:.3e}")
+        tag = f"P={P} f={f} T={T}"
+        arms += [
+            (f"mx8_unpack ({tag})", lambda pk=packed, bl=block: ops.mx8_unpack(pk, bl)),
+            (f"segment_gram on the block ({tag})", lambda bl=block: ops.segment_gram(bl, seg)),
+            (f"mx8_segment_gram ({tag})", lambda pk=packed: ops.mx8_segment_gram(pk, seg)),
+            (f"segment_mean_around on the block ({tag})",
+             lambda bl=block, s=sel, k=plan: ops.segment_mean_around(bl, s, seg, *k, ref)),
+            (f"mx8_segment_mean_around ({tag})",
+             lambda pk=packed, s=sel, k=plan: ops.mx8_segment_mean_around(pk, s, seg, *k, out)),
+        ]
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn in arms:
+            ms = ev_ms(fn, iters=20, warmup=5)
+            if name not in times:
+                times[name] = []
+                order.append(name)
+            times[name].append(ms)
+            print(f"{name:52} {ms*1e3:9.1f} us")
+    print("# min - max over rounds")
+    for name in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:52} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -790,6 +862,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("SIGN_ONLY") == "1":
         sign_majority_compare()
+        raise SystemExit(0)
+    if os.environ.get("MX8_GRAM_ONLY") == "1":
+        mx8_gram_compare()
         raise SystemExit(0)
     if os.environ.get("MX8_FUSED_ONLY") == "1":
         mx8_fused_compare()
