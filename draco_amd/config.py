@@ -39,7 +39,7 @@ class Config:
     adversarial: int = 1              # parity flag (err magnitude switch; reference hardcodes -100)
     worker_fail: int = 2
     group_size: int = 5
-    compress_grad: str = "none"       # none|bf16|sign|mx8 wire format of the gradient exchange (bf16
+    compress_grad: str = "none"       # none|bf16|sign|mx8|mx4 wire format of the gradient exchange (bf16
                                       # replaces the reference's blosc/snappy CPU compression,
                                       # SURVEY §2.2 K12, for maj_vote / cyclic; sign is signSGD
                                       # with majority vote, arXiv:1810.05291: 2 bits per element,
@@ -51,7 +51,10 @@ class Config:
                                       # alie/ipm, nnm and worker momentum run behind it;
                                       # baseline approach, colocated topology; mode normal
                                       # becomes the exchange-path mean, at most 64 workers;
-                                      # see parallel/aggregators.Aggregator.wire)
+                                      # see parallel/aggregators.Aggregator.wire; mx4 is the
+                                      # MXFP4 wire, one E2M1 nibble per element and the same
+                                      # scales, under the same conditions as mx8, rounded as
+                                      # mx_rounding says)
     checkpoint_step: int = 0
     optimizer: str = "sgd"            # sgd|adam (fused flat kernels, optim/flat_sgd.py)
 
@@ -107,6 +110,11 @@ class Config:
                                    # approach, colocated topology, 2*worker_fail < P <= 32;
                                    # see parallel/mixing.py, ops.mix_rows_)
 
+    mx_rounding: str = "stochastic"   # stochastic|nearest: the rounding of --compress-grad mx4
+                                      # (stochastic is unbiased per element, its random bits
+                                      # a stateless hash of seed, rank and a row count that
+                                      # is not checkpointed); any other wire rejects nearest
+
     def sanity(self):
         from .coding.collusion import COLLUDING_MODES
 
@@ -146,6 +154,28 @@ class Config:
                 raise ValueError(
                     what + "cannot be combined with --health-timeout (the packed exchange "
                     "of a survivor world is not built)")
+
+        if self.compress_grad == "mx4":
+            what = ("compress-grad 'mx4' (the MXFP4 block-scaled 4-bit wire of the baseline "
+                    "rules): ")
+            if self.approach != "baseline":
+                raise ValueError(
+                    what + "needs --approach baseline (one code quantum is up to 50% relative, "
+                    "far outside the vote tolerance of maj_vote and the locator thresholds of "
+                    f"cyclic), got {self.approach!r}")
+            if self.topology == "ps":
+                raise ValueError(what + "needs the colocated topology, not --topology ps")
+            if self.health_timeout > 0:
+                raise ValueError(
+                    what + "cannot be combined with --health-timeout (the packed exchange "
+                    "of a survivor world is not built)")
+        if self.mx_rounding not in ("stochastic", "nearest"):
+            raise ValueError(f"mx-rounding must be stochastic or nearest, got {self.mx_rounding!r}")
+        if self.mx_rounding != "stochastic" and self.compress_grad != "mx4":
+            raise ValueError(
+                f"mx-rounding {self.mx_rounding!r} is read by --compress-grad mx4 alone (mx8 "
+                f"rounds to nearest, the other wires do not round), got compress-grad "
+                f"{self.compress_grad!r}")
 
         if self.pre_aggregation != "none":
             what = f"pre-aggregation {self.pre_aggregation!r}: "
@@ -215,7 +245,11 @@ _HELP = {
     "compress_grad": "none | bf16 (alias compress: bf16 wire for maj_vote / cyclic) | sign "
                      "(signSGD with majority vote: 2-bit sign wire, --approach baseline --mode "
                      "normal) | mx8 (MXFP8 block-scaled 8-bit wire: E4M3 codes, one scale per "
-                     "32 elements; every --approach baseline rule, colocated topology)",
+                     "32 elements; every --approach baseline rule, colocated topology) | mx4 "
+                     "(MXFP4 4-bit wire: E2M1 codes and the same scales, same conditions, "
+                     "rounded as --mx-rounding says)",
+    "mx_rounding": "stochastic (default, unbiased per element) | nearest: the rounding of "
+                   "--compress-grad mx4; rejected with any other wire unless stochastic",
 }
 
 

@@ -28,6 +28,9 @@ __all__ = [
     "mx8_column_mean_around",
     "mx8_segment_gram",
     "mx8_segment_mean_around",
+    "mx4_pack",
+    "mx4_unpack",
+    "mx4_chunk_bytes",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -264,6 +267,40 @@ def mx8_segment_mean_around(packed, sel, seg, keep, clo, chi, out):
                                     int(keep), int(clo), int(chi), out)
         return
     fallback.mx8_segment_mean_around(packed, sel, seg, int(keep), int(clo), int(chi), out)
+
+
+def mx4_chunk_bytes(chunk):
+    """Bytes of one packed record of the mx4 wire: chunk / 2 + round_up(chunk / 32, 16)."""
+    return fallback.mx4_chunk_bytes(int(chunk))
+
+
+def mx4_pack(g, out, chunk, seed=None):
+    """The MXFP4 wire format: out (n / chunk * mx4_chunk_bytes(chunk),) uint8 = the packed
+    records of g (n,) fp32, n % chunk == 0, chunk % 64 == 0: one E2M1 nibble per element and
+    one E8M0 scale per 32 elements; a block with a NaN / Inf element decodes to 32 NaNs.
+    seed=None rounds to nearest; an int seed (taken mod 2^64) rounds stochastically,
+    unbiased per element, from a stateless hash of (seed, element index), so the bytes do not
+    depend on the device or the launch.  The seed reaches the kernel by value.  The kernel
+    (gfx950 scaled FP4 converts for nearest, integer VALU rounding for stochastic, block amax
+    by DPP) and the fallback write the same bytes.  Format: above k_mx4_pack in
+    draco_kernels.hip; definition and checks: fallback.mx4_pack."""
+    ext = _native_for(g)
+    if ext is not None:
+        ext.mx4_pack(g, out, int(chunk), seed is not None,
+                     0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return
+    fallback.mx4_pack(g, out, int(chunk), seed)
+
+
+def mx4_unpack(packed, out):
+    """out (P, chunk) fp32 = the decoded rows of packed (P, mx4_chunk_bytes(chunk)) uint8.
+    Every byte pattern decodes to an fp32 value, NaN or +-Inf; kernel and fallback agree
+    bit for bit (NaNs as NaNs).  Definition and checks: fallback.mx4_unpack."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx4_unpack(packed, out)
+        return
+    fallback.mx4_unpack(packed, out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

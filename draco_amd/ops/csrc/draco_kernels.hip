@@ -21,6 +21,8 @@
 // the column sort on that wire: it reads the packed records, four columns per lane.
 // k_mx8_seg_gram / k_mx8_seg_mean_around are Multi-Krum's and Bulyan's two steps on it: the
 // Gram decodes a lane's MX block in registers and multiplies on the matrix unit.
+// k_mx4_pack / k_mx4_unpack (the MXFP4 4-bit wire) use the scaled FP4 converts; a block is
+// one quad of lanes, and the stochastic rounding is integer VALU work on a stateless hash.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -1959,9 +1961,11 @@ k_mx8_unpack(const unsigned char *__restrict__ packed, float4 *__restrict__ out,
   }
 }
 
-// the checks shared by mx8_pack and mx8_unpack; returns the units (wave loads) of the call
-static inline int check_mx8(const char *op, const torch::Tensor &vals, const torch::Tensor &bytes,
-                            long chunk, long records) {
+// the checks shared by the pack and unpack ops of the block-scaled wires (mx8 and mx4):
+// `records` records of `cbytes` bytes for `chunk` elements each, walked in units (wave loads)
+// of `unit` elements, `trip` of them per wave per trip; returns the units of the call
+static inline int check_mx(const char *op, const torch::Tensor &vals, const torch::Tensor &bytes,
+                           long chunk, long records, long cbytes, long unit, long trip) {
   CHECK_IN(vals);
   CHECK_IN(bytes);
   TORCH_CHECK(vals.device() == bytes.device(), op, ": tensors must be on one device");
@@ -1970,13 +1974,18 @@ static inline int check_mx8(const char *op, const torch::Tensor &vals, const tor
   TORCH_CHECK(chunk >= 0 && chunk % 64 == 0, op, ": chunk must be a multiple of 64, got ", chunk);
   TORCH_CHECK(vals.numel() == records * chunk, op, ": values must hold ", records, " x ", chunk,
               " elements, got ", vals.numel());
-  TORCH_CHECK(bytes.numel() == records * mx8_chunk_bytes(chunk), op, ": packed data must hold ",
-              records, " records of ", mx8_chunk_bytes(chunk), " bytes, got ", bytes.numel());
+  TORCH_CHECK(bytes.numel() == records * cbytes, op, ": packed data must hold ",
+              records, " records of ", cbytes, " bytes, got ", bytes.numel());
   TORCH_CHECK((uintptr_t)vals.data_ptr() % 16 == 0 && (uintptr_t)bytes.data_ptr() % 16 == 0, op,
               ": tensors must be 16-byte aligned");
-  long units = records * ((chunk + 255) / 256);
-  TORCH_CHECK(units <= 0x7fffffffL - MX8_TRIP, op, ": ", units, " wave loads exceed the 32-bit unit index");
+  long units = records * ((chunk + unit - 1) / unit);
+  TORCH_CHECK(units <= 0x7fffffffL - trip, op, ": ", units, " wave loads exceed the 32-bit unit index");
   return (int)units;
+}
+
+static inline int check_mx8(const char *op, const torch::Tensor &vals, const torch::Tensor &bytes,
+                            long chunk, long records) {
+  return check_mx(op, vals, bytes, chunk, records, mx8_chunk_bytes(chunk), 256, MX8_TRIP);
 }
 
 void mx8_pack(torch::Tensor g, torch::Tensor out, long chunk) {
@@ -2512,6 +2521,289 @@ void mx8_segment_mean_around(torch::Tensor packed, torch::Tensor sel, torch::Ten
   });
 }
 
+// --------------------------------------------------------------------------- mx4 wire
+// A 4-bit block-scaled wire format for gradient rows: OCP Microscaling MXFP4, E2M1 elements
+// with one E8M0 scale per 32 elements, rounded to nearest or STOCHASTICALLY (unbiased per
+// element).  Like the mx8 wire it decodes to an ordinary fp32 block that every rule reads.
+//
+// WIRE FORMAT (the one description; fallback.mx4_pack / mx4_unpack produce the same bytes).
+// Element code: one nibble, E2M1: 1 sign, 2 exponent (bias 1), 1 mantissa bit; the
+// magnitudes of codes 0..7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6; no NaN or Inf codes.  Element 2k
+// of a row is the low nibble of byte k, element 2k+1 the high nibble.  Block: 32 consecutive
+// elements share a scale byte s, an E8M0 exponent meaning 2^(s-127); s = 0xFF is NaN for the
+// whole block.
+//   Encoding a block: if any element is NaN or +-Inf the scale byte is 0xFF (the format's
+// price: one non-finite element costs that worker 32 coordinates of NaN, never more, and a
+// non-finite element stays non-finite); the 16 code bytes are still written as below, with
+// a non-finite element coded as 0 with its sign, and decoders ignore them.  amax = the
+// largest |x| over the block's finite elements; e = the smallest integer with
+// amax / 2^e <= 6, read off amax's bits: e = exponent(amax) - 2, plus 1 if the mantissa
+// field exceeds 0x400000 (6 = 1.5 * 2^2); e is clamped to >= -125 (also taken when amax = 0)
+// and s = e + 127 is in [2, 253].  Nothing saturates.  x's sign bit is kept, also for -0.0
+// and for values that round to zero.
+//   Rounding of t = |x| * 2^-e (t < 2^-126 counts as 0).  Nearest: the nearest grid value,
+// ties to the even code.  Stochastic: with lo the largest grid value <= t, hi the next one
+// and step = hi - lo, round up iff float(r) < ((t - lo) / step) * 2^24 for a 24-bit random
+// integer r (every operation of that line is exact in fp32): P(up) is within 2^-24 of
+// (t - lo) / step, and t on the grid never moves.  r of element i of the row (i mod 2^32)
+// under a 64-bit seed is a stateless hash, whatever the launch geometry:
+// h(a): a ^= a >> 16; a *= 0x7feb352d; a ^= a >> 15; a *= 0x846ca68b; a ^= a >> 16 (32-bit),
+// key = h(seed_lo ^ h(seed_hi + 0x9e3779b9)), r = h(i ^ key) >> 8.
+//   Both roundings are stated in integers on x's significand M (24 bits, hidden bit
+// included) and q = max(exponent field, 1) - s, t = M * 2^(q-23), q <= 2: the grid steps
+// by 2^(22-sh) * t / M with sh = 22 - min(q, 0), so lo's code is (M >> sh) + 2 * max(q, 0),
+// the next code is hi's, and (t - lo) / step = frac / 2^sh with frac = M mod 2^sh.
+//   Decoding: s = 0xFF gives 32 NaNs; otherwise s is clamped to >= 2 and value = code value
+// * 2^(s-127) in fp32.  With the clamp every finite non-zero result is a normal fp32 number
+// (0.5 * 2^-125 = 2^-126); an overflowing product (6 * 2^127) is +-Inf.  Every byte pattern
+// decodes to an fp32 value, NaN or +-Inf.
+//   Packed row: packed against a chunk (the shard length) with n % chunk == 0 and
+// chunk % 64 == 0 into n / chunk records of chunk_bytes = chunk / 2 + round_up(chunk / 32,
+// 16) bytes: the code bytes, the scale bytes, zero padding.  Records and scale runs start
+// 16-byte aligned, a record depends on its chunk's elements alone, and the even all_to_all
+// split of a packed row lands each rank's codes and scales on it, as for mx8.
+//   Error: nearest, |decode(encode(x)) - x| <= max(|x| / 4, X / 4) with X = 2^e < amax / 3;
+// stochastic, below one grid step (at most max(|x| / 2, X / 2)) and E[decode(encode(x))] = x
+// up to 2^-24 of a step.
+//
+// The gfx950 scaled converts (v_cvt_scalef32_pk_fp4_f32 / v_cvt_scalef32_pk_f32_fp4) do the
+// element work of the nearest encode and of the decode.  Measured once on the MI355X with a
+// stand-alone probe program that is not in the tree (the exact tests of
+// tests/test_mx4_gpu.py are what stays), against the integer statement above: the encode,
+// issued as the kernel issues it (four converts filling bytes 0..3 of a dword, source 0 in
+// the low nibble), gives the format's nibble for every fp32 bit pattern of either sign that
+// is in range for scales 2, 3, 60, 127, 200, 252 and 253 (nearest, ties to the even code,
+// fp32 subnormal inputs honoured, sign of zero and of values that round to zero kept); the
+// decode is exact for all 256 code bytes at every scale 2..254, the overflow to +-Inf and
+// -0.0 included.  Neither needed a patch.  The scale operand is the fp32 number 2^(s-127),
+// always normal here.  Non-finite elements reach the convert as signed zeros and
+// out-of-range inputs are never converted, so what the instruction does with them is not
+// relied on.  The stochastic rounding is NOT the hardware's v_cvt_scalef32_sr_pk_fp4_f32
+// (its use of the random operand is not documented and was not probed): it is the integer
+// statement above in plain VALU arithmetic.
+//
+// Both kernels walk "units": a unit is 512 consecutive elements of one record, eight per
+// lane, MX4_TRIP units per wave per trip with all loads issued before any conversion.
+// chunk % 64 == 0: in k_mx4_pack a lane's eight consecutive elements and a 32-element block
+// (one quad of lanes) are inside or outside the record as a whole, and a unit's 16 scale
+// bytes are one 16-byte store: round_up(chunk / 32, 16) is whole units of them.
+#define MX4_TRIP 2
+
+static inline long mx4_chunk_bytes(long chunk) { return chunk / 2 + (chunk / 32 + 15) / 16 * 16; }
+
+__device__ __forceinline__ unsigned mx4_hash(unsigned a) {
+  a ^= a >> 16; a *= 0x7feb352du; a ^= a >> 15; a *= 0x846ca68bu; a ^= a >> 16;
+  return a;
+}
+
+// max over the four lanes of a block, in every one of them: two quad permutes
+__device__ __forceinline__ unsigned mx4_block_max(unsigned v) {
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));  // lane ^ 1
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));  // lane ^ 2
+  return v;
+}
+
+// the stochastically rounded code (no sign) of a finite magnitude `a` (fp32 bits) in a block
+// of scale byte s, by the integer statement above; r: the element's 24 random bits
+__device__ __forceinline__ unsigned mx4_code_sr(unsigned a, int s, unsigned r) {
+  int ex = (int)(a >> 23);
+  unsigned M = (a & 0x7fffffu) | (ex ? 0x800000u : 0u);
+  int q = max(ex, 1) - s;
+  int sh = 22 - min(q, 0);  // 22 .. 274
+  unsigned lo = (M >> min(sh, 31)) + 2u * (unsigned)max(q, 0);
+  unsigned frac = M & ((1u << min(sh, 31)) - 1u);
+  // up iff r < frac * 2^24 / 2^sh: an integer threshold either way (past sh = 48 it is r == 0)
+  int d = min(sh - 24, 24);
+  unsigned thr = sh <= 24 ? frac << (24 - sh) : (frac + (1u << d) - 1u) >> d;
+  bool tiny = sh > 125 && (M >> min(sh - 125, 31)) == 0u;  // t < 2^-126
+  return lo + (unsigned)(r < thr && !tiny);
+}
+
+// k_mx4_pack<SR>: one streaming pass, 4 B read and ~0.53 B written per element, no LDS, no
+// atomics.  Per unit a lane holds eight elements: non-finite ones are replaced by a signed
+// zero (their code) and flagged, the finite amax and the flag are reduced over the quad by
+// DPP, the scale byte comes from amax's exponent and mantissa fields.  Nearest (SR = false):
+// four scaled converts give the lane's dword of codes.  Stochastic: eight integer roundings
+// (mx4_code_sr), each with its own hash of the element index.  A wave stores 256 contiguous
+// code bytes.  The unit's 16 scale bytes: every lane shifts its block's byte to the block's
+// place in its row's dword (a row is 16 lanes, four blocks), two mirror DPP steps OR the
+// row's four bytes together in every lane, four v_readlane collect the rows, and lane 0
+// stores one 16-byte vector.  An outside block contributes 0, which is the record's padding.
+// The loop's trip count is wave-uniform: every lane runs the DPP and readlane steps.
+template <bool SR>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx4_pack(const uint4 *__restrict__ g, unsigned char *__restrict__ out, long chunk, long cbytes,
+           int upr, int units, unsigned seed_lo, unsigned seed_hi) {
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const unsigned place = 8u * ((unsigned)(lane >> 2) & 3u);
+  const unsigned key = mx4_hash(seed_lo ^ mx4_hash(seed_hi + 0x9e3779b9u));
+  long u0 = (blockIdx.x * (long)(NTHREADS / WAVE) + wave) * MX4_TRIP;
+  long ustride = gridDim.x * (long)(NTHREADS / WAVE) * MX4_TRIP;
+  for (; u0 < units; u0 += ustride) {
+    // u0 < units fits an int (checked on the host): a 32-bit division, once per trip
+    const int u = (int)u0;
+    int r = u / upr, j = u - r * upr;  // record, unit of the record
+    uint4 v[MX4_TRIP][2];
+    long base[MX4_TRIP];  // byte offset of the unit's record; -1: no such unit
+    long first[MX4_TRIP];  // the row index of the record's first element
+    int uj[MX4_TRIP];
+#pragma unroll
+    for (int t = 0; t < MX4_TRIP; ++t) {
+      long o = (long)j * 512 + 8 * lane;  // the lane's first element in the record
+      base[t] = u0 + t < units ? r * cbytes : -1;
+      first[t] = r * chunk;
+      uj[t] = j;
+      v[t][0] = v[t][1] = make_uint4(0u, 0u, 0u, 0u);
+      if (base[t] >= 0 && o < chunk) {
+        v[t][0] = g[(first[t] + o) / 4];
+        v[t][1] = g[(first[t] + o) / 4 + 1];
+      }
+      if (++j == upr) { j = 0; ++r; }
+    }
+#pragma unroll
+    for (int t = 0; t < MX4_TRIP; ++t) {
+      long o = (long)uj[t] * 512 + 8 * lane;
+      bool in = base[t] >= 0 && o < chunk;
+      unsigned x[8] = {v[t][0].x, v[t][0].y, v[t][0].z, v[t][0].w,
+                       v[t][1].x, v[t][1].y, v[t][1].z, v[t][1].w};
+      unsigned amax = 0u, bad = 0u;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {  // NaN, +-Inf: a zero with the element's sign, and the flag
+        unsigned a = x[k] & 0x7fffffffu;
+        bool fin = a < 0x7f800000u;
+        a = fin ? a : 0u;
+        amax = max(amax, a);
+        bad |= (unsigned)!fin;
+        x[k] = a | (x[k] & 0x80000000u);
+      }
+      amax = mx4_block_max(amax);
+      bad = mx4_block_max(bad);
+      int s = (int)(amax >> 23) - 2 + ((amax & 0x7fffffu) > 0x400000u);
+      s = max(s, 2);
+      unsigned codes = 0u;
+      if constexpr (SR) {
+        const unsigned i0 = (unsigned)(first[t] + o);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          unsigned r24 = mx4_hash((i0 + k) ^ key) >> 8;
+          codes |= (mx4_code_sr(x[k] & 0x7fffffffu, s, r24) | (x[k] >> 28 & 8u)) << (4 * k);
+        }
+      } else {
+        float scale = __uint_as_float((unsigned)s << 23);
+        codes = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(codes, __uint_as_float(x[0]), __uint_as_float(x[1]), scale, 0);
+        codes = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(codes, __uint_as_float(x[2]), __uint_as_float(x[3]), scale, 1);
+        codes = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(codes, __uint_as_float(x[4]), __uint_as_float(x[5]), scale, 2);
+        codes = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(codes, __uint_as_float(x[6]), __uint_as_float(x[7]), scale, 3);
+      }
+      if (in) *reinterpret_cast<unsigned *>(out + base[t] + o / 2) = codes;
+      unsigned w = (in ? (bad ? 0xffu : (unsigned)s) : 0u) << place;
+      w |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0x141, 0xF, 0xF, false);  // 7 - lane
+      w |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0x140, 0xF, 0xF, false);  // 15 - lane
+      uint4 sc = make_uint4((unsigned)__builtin_amdgcn_readlane((int)w, 0),
+                            (unsigned)__builtin_amdgcn_readlane((int)w, 16),
+                            (unsigned)__builtin_amdgcn_readlane((int)w, 32),
+                            (unsigned)__builtin_amdgcn_readlane((int)w, 48));
+      if (lane == 0 && base[t] >= 0)
+        *reinterpret_cast<uint4 *>(out + base[t] + chunk / 2 + 16L * uj[t]) = sc;
+    }
+  }
+}
+
+// k_mx4_unpack: ~0.53 B read and 4 B written per element.  The writes are what the kernel
+// moves, so the lanes are laid out for them and not as in k_mx4_pack: of a unit's 128 float4 a
+// lane owns numbers `lane` and `64 + lane`, so that each of its two stores is 1 KB contiguous
+// per wave (a lane storing two adjacent float4 fills half of every cache line per store, which
+// measured 25% slower than k_mx8_unpack; this layout is still 6 to 11% slower than it, see
+// profiles/kernel_bw_mx4.txt).  It reads the two 16-bit code pairs of
+// those float4 (128 contiguous bytes per wave each) and their blocks' scale bytes (one byte
+// shared by eight lanes, a cached byte load), and runs four scaled converts, byte selects 0
+// and 1 of each pair.  The load loop only loads: combining the two pairs into one dword there
+// made the compiler wait for each load before issuing the next (three s_waitcnt vmcnt per
+// trip, read off the ISA).  The rows are flattened into the unit index.  No cross-lane step,
+// so an outside lane simply skips.
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx4_unpack(const unsigned char *__restrict__ packed, float4 *__restrict__ out, long chunk,
+             long cbytes, int upr, int units) {
+  const int lane = threadIdx.x % WAVE;
+  long u0 = (blockIdx.x * (long)(NTHREADS / WAVE) + threadIdx.x / WAVE) * MX4_TRIP;
+  long ustride = gridDim.x * (long)(NTHREADS / WAVE) * MX4_TRIP;
+  for (; u0 < units; u0 += ustride) {
+    const int u = (int)u0;  // as in k_mx4_pack
+    int r = u / upr, j = u - r * upr;
+    unsigned codes[MX4_TRIP][2], sbyte[MX4_TRIP][2];  // loaded values are not touched in this loop
+    long dst[MX4_TRIP];  // float4 index in out of the lane's first float4; -1: nothing to do
+    bool second[MX4_TRIP];  // the lane's second float4 is inside the record too
+#pragma unroll
+    for (int t = 0; t < MX4_TRIP; ++t) {
+      long o = (long)j * 512 + 4 * lane;  // the first float4's elements; the second: o + 256
+      bool in = u0 + t < units && o < chunk;
+      second[t] = in && o + 256 < chunk;
+      dst[t] = in ? (r * chunk + o) / 4 : -1;
+      codes[t][0] = codes[t][1] = sbyte[t][0] = sbyte[t][1] = 0u;
+      const unsigned char *rec = packed + r * cbytes;
+      if (in) {
+        codes[t][0] = *reinterpret_cast<const unsigned short *>(rec + o / 2);
+        sbyte[t][0] = rec[chunk / 2 + o / 32];
+      }
+      if (second[t]) {
+        codes[t][1] = *reinterpret_cast<const unsigned short *>(rec + o / 2 + 128);
+        sbyte[t][1] = rec[chunk / 2 + o / 32 + 8];
+      }
+      if (++j == upr) { j = 0; ++r; }
+    }
+#pragma unroll
+    for (int t = 0; t < MX4_TRIP; ++t) {
+      const float nan = __uint_as_float(0x7fc00000u);
+      float s0 = __uint_as_float(max(sbyte[t][0], 2u) << 23);
+      float s1 = __uint_as_float(max(sbyte[t][1], 2u) << 23);
+      mx8_v2f a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes[t][0], s0, 0);
+      mx8_v2f b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes[t][0], s0, 1);
+      mx8_v2f c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes[t][1], s1, 0);
+      mx8_v2f d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes[t][1], s1, 1);
+      float4 y0 = make_float4(a.x, a.y, b.x, b.y), y1 = make_float4(c.x, c.y, d.x, d.y);
+      if (sbyte[t][0] == 0xffu) y0.x = y0.y = y0.z = y0.w = nan;
+      if (sbyte[t][1] == 0xffu) y1.x = y1.y = y1.z = y1.w = nan;
+      if (dst[t] >= 0) out[dst[t]] = y0;
+      if (second[t]) out[dst[t] + 64] = y1;
+    }
+  }
+}
+
+static inline int check_mx4(const char *op, const torch::Tensor &vals, const torch::Tensor &bytes,
+                            long chunk, long records) {
+  return check_mx(op, vals, bytes, chunk, records, mx4_chunk_bytes(chunk), 512, MX4_TRIP);
+}
+
+// seed: read only with stochastic = true; it reaches the kernel by value, as two words
+void mx4_pack(torch::Tensor g, torch::Tensor out, long chunk, bool stochastic, uint64_t seed) {
+  long n = g.numel();
+  TORCH_CHECK(g.dim() == 1 && out.dim() == 1, "mx4_pack: g and out must be 1D");
+  TORCH_CHECK(chunk > 0 ? n % chunk == 0 : n == 0, "mx4_pack: length ", n,
+              " is not a multiple of chunk ", chunk);
+  int units = check_mx4("mx4_pack", g, out, chunk, chunk > 0 ? n / chunk : 0);
+  if (units == 0) return;
+  int upr = (int)((chunk + 511) / 512);
+  int blocks = n_blocks((units + MX4_TRIP - 1) / MX4_TRIP, NTHREADS / WAVE);
+  launch(stochastic ? k_mx4_pack<true> : k_mx4_pack<false>, dim3(blocks), 0,
+         (const uint4 *)g.data_ptr<float>(), out.data_ptr<uint8_t>(), chunk, mx4_chunk_bytes(chunk),
+         upr, units, (unsigned)seed, (unsigned)(seed >> 32));
+}
+
+void mx4_unpack(torch::Tensor packed, torch::Tensor out) {
+  TORCH_CHECK(packed.dim() == 2 && out.dim() == 2 && packed.size(0) == out.size(0),
+              "mx4_unpack: packed must be (P, chunk_bytes) and out (P, chunk)");
+  long P = out.size(0), chunk = out.size(1);
+  int units = check_mx4("mx4_unpack", out, packed, chunk, P);
+  TORCH_CHECK(packed.size(1) == mx4_chunk_bytes(chunk), "mx4_unpack: packed rows must have ",
+              mx4_chunk_bytes(chunk), " bytes for chunk ", chunk, ", got ", packed.size(1));
+  if (units == 0) return;  // P = 0 or chunk = 0: no launch
+  int upr = (int)((chunk + 511) / 512);
+  int blocks = n_blocks((units + MX4_TRIP - 1) / MX4_TRIP, NTHREADS / WAVE);
+  launch(k_mx4_unpack, dim3(blocks), 0, packed.data_ptr<uint8_t>(), (float4 *)out.data_ptr<float>(),
+         chunk, mx4_chunk_bytes(chunk), upr, units);
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -2550,4 +2842,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx8_column_mean_around", &mx8_column_mean_around);
   m.def("mx8_segment_gram", &mx8_segment_gram);
   m.def("mx8_segment_mean_around", &mx8_segment_mean_around);
+  m.def("mx4_pack", &mx4_pack);
+  m.def("mx4_unpack", &mx4_unpack);
 }

@@ -397,7 +397,8 @@ def mx8_chunk_bytes(chunk: int) -> int:
     return chunk + (chunk // 32 + 15) // 16 * 16
 
 
-def _check_mx8(op: str, vals: torch.Tensor, data: torch.Tensor, chunk: int, records: int) -> None:
+def _check_mx8(op: str, vals: torch.Tensor, data: torch.Tensor, chunk: int, records: int,
+               chunk_bytes=mx8_chunk_bytes) -> None:
     if vals.dtype != torch.float32:
         raise ValueError(f"{op}: values must be fp32, got {vals.dtype}")
     if data.dtype != torch.uint8:
@@ -411,9 +412,9 @@ def _check_mx8(op: str, vals: torch.Tensor, data: torch.Tensor, chunk: int, reco
     if vals.numel() != records * chunk:
         raise ValueError(f"{op}: values must hold {records} x {chunk} elements, got "
                          f"{vals.numel()}")
-    if data.numel() != records * mx8_chunk_bytes(chunk):
+    if data.numel() != records * chunk_bytes(chunk):
         raise ValueError(f"{op}: packed data must hold {records} records of "
-                         f"{mx8_chunk_bytes(chunk)} bytes, got {data.numel()}")
+                         f"{chunk_bytes(chunk)} bytes, got {data.numel()}")
 
 
 @torch.no_grad()
@@ -472,6 +473,100 @@ def mx8_unpack(packed: torch.Tensor, out: torch.Tensor) -> None:
     scale = (s.clamp(min=10) << 23).view(torch.float32)  # 2^(s-127), a normal fp32 number
     scale = torch.where(s == 0xFF, torch.full_like(scale, float("nan")), scale)
     out.copy_(table[packed[:, :chunk].long()] * scale.repeat_interleave(32, dim=1))
+
+
+# --------------------------------------------------------------------- mx4 wire
+def mx4_chunk_bytes(chunk: int) -> int:
+    """Bytes of one packed record: chunk/2 code bytes, chunk/32 scales, zero padding to 16."""
+    return chunk // 2 + (chunk // 32 + 15) // 16 * 16
+
+
+def _mx4_hash(a: torch.Tensor) -> torch.Tensor:
+    """h of the mx4 format on int64 tensors holding 32-bit values (products wrap mod 2^64,
+    which keeps the low 32 bits)."""
+    a = a ^ (a >> 16)
+    a = (a * 0x7FEB352D) & 0xFFFFFFFF
+    a = a ^ (a >> 15)
+    a = (a * 0x846CA68B) & 0xFFFFFFFF
+    return a ^ (a >> 16)
+
+
+@torch.no_grad()
+def mx4_pack(g: torch.Tensor, out: torch.Tensor, chunk: int, seed=None) -> None:
+    """The MXFP4 wire (E2M1 nibbles, one E8M0 scale per 32 elements): out = the n / chunk
+    packed records of g.  g: (n,) fp32, n % chunk == 0, chunk % 64 == 0; out:
+    (n / chunk * mx4_chunk_bytes(chunk),) uint8.  seed=None rounds to nearest (ties to the
+    even code); an int seed rounds stochastically, unbiased per element, with the 24 random
+    bits of element i a stateless hash of (seed mod 2^64, i).  The format is described once,
+    above k_mx4_pack in draco_kernels.hip; this is its executable definition, in integer
+    arithmetic on the fp32 bit patterns, and the kernel writes the same bytes."""
+    n = g.numel()
+    if g.dim() != 1 or out.dim() != 1:
+        raise ValueError("mx4_pack: g and out must be 1D")
+    if (n % chunk != 0) if chunk > 0 else (n != 0):
+        raise ValueError(f"mx4_pack: length {n} is not a multiple of chunk {chunk}")
+    records = n // chunk if chunk > 0 else 0
+    _check_mx8("mx4_pack", g, out, chunk, records, mx4_chunk_bytes)
+    if n == 0:
+        return
+    u = g.view(torch.int32).to(torch.int64)
+    a, sign = u & 0x7FFFFFFF, (u >> 28) & 8
+    fin = a < 0x7F800000
+    a = torch.where(fin, a, torch.zeros_like(a))  # a non-finite element: code 0 with its sign
+    amax = a.view(-1, 32).amax(dim=1)
+    # s = e + 127 with e = exponent(amax) - 2, plus 1 past 1.5 * 2^exponent; e >= -125
+    s = ((amax >> 23) - 2 + ((amax & 0x7FFFFF) > 0x400000)).clamp_(min=2)
+    ex, m = a >> 23, a & 0x7FFFFF
+    m = torch.where(ex > 0, m | 0x800000, m)  # the 24-bit significand M; subnormals have ex = 1
+    q = ex.clamp(min=1) - s.repeat_interleave(32)  # t = M * 2^(q-23), q <= 2
+    sh = 22 - q.clamp(max=0)  # t / step = M / 2^sh: step 0.5 below 2, then 1, then 2
+    shc = sh.clamp(max=31)  # M < 2^24: past 24 the quotient is 0 and the remainder M
+    frac = m & ((torch.ones_like(shc) << shc) - 1)
+    code = (m >> shc) + 2 * q.clamp(min=0)  # lo's code; hi's is the next one
+    if seed is None:
+        half = torch.ones_like(shc) << (shc - 1)
+        up = (frac > half) | ((frac == half) & ((code & 1) == 1))
+    else:
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        hi_word = torch.tensor(((seed >> 32) + 0x9E3779B9) & 0xFFFFFFFF, device=g.device)
+        key = _mx4_hash((seed & 0xFFFFFFFF) ^ _mx4_hash(hi_word))
+        i = torch.arange(n, device=g.device) & 0xFFFFFFFF
+        r = _mx4_hash(i ^ key) >> 8
+        # up iff r < frac * 2^24 / 2^sh, in integers on either side of sh = 24
+        d = (sh - 24).clamp(min=0, max=24)
+        thr = torch.where(sh <= 24, frac << (24 - sh).clamp(min=0),
+                          (frac + (torch.ones_like(d) << d) - 1) >> d)
+        tiny = (sh > 125) & ((m >> (sh - 125).clamp(min=0, max=31)) == 0)  # t < 2^-126
+        up = (r < thr) & ~tiny
+    code = (code + up) | sign
+    bad = (~fin).view(-1, 32).any(dim=1)
+    s = torch.where(bad, torch.full_like(s, 0xFF), s)
+    rec = out.view(records, -1)
+    code = code.view(records, chunk // 2, 2)
+    rec[:, : chunk // 2] = (code[:, :, 0] | (code[:, :, 1] << 4)).to(torch.uint8)
+    rec[:, chunk // 2: chunk // 2 + chunk // 32] = s.view(records, -1).to(torch.uint8)
+    rec[:, chunk // 2 + chunk // 32:] = 0
+
+
+@torch.no_grad()
+def mx4_unpack(packed: torch.Tensor, out: torch.Tensor) -> None:
+    """out (P, chunk) fp32 = the decoded rows of packed (P, mx4_chunk_bytes(chunk)) uint8 in
+    mx4_pack's format.  Any bytes decode: a scale byte below 2 counts as 2, 0xFF makes the
+    block NaN, an overflowing product is +-Inf.  P == 0 or chunk == 0 returns at once."""
+    if packed.dim() != 2 or out.dim() != 2 or packed.shape[0] != out.shape[0]:
+        raise ValueError("mx4_unpack: packed must be (P, chunk_bytes) and out (P, chunk)")
+    P, chunk = out.shape
+    _check_mx8("mx4_unpack", out, packed, chunk, P, mx4_chunk_bytes)
+    if P == 0 or chunk == 0:
+        return
+    table = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], device=out.device)
+    table = torch.cat([table, -table])
+    b = packed[:, : chunk // 2].long()
+    codes = torch.stack([b & 15, b >> 4], dim=2).view(P, chunk)  # element 2k: the low nibble
+    s = packed[:, chunk // 2: chunk // 2 + chunk // 32].to(torch.int32)
+    scale = (s.clamp(min=2) << 23).view(torch.float32)  # 2^(s-127), a normal fp32 number
+    scale = torch.where(s == 0xFF, torch.full_like(scale, float("nan")), scale)
+    out.copy_(table[codes] * scale.repeat_interleave(32, dim=1))
 
 
 # --------------------------------------------------------------------- vote

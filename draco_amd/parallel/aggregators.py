@@ -86,7 +86,13 @@ class Aggregator:
     # bytes and their kernels decode while they load.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
     # stays non-finite.  With one rank the rows are still packed and unpacked.  The
     # bucketed path is not built for this wire: the row ships whole from aggregate().
+    # "mx4" (--compress-grad mx4) takes the same route with ops.mx4_pack / ops.mx4_unpack: one
+    # E2M1 nibble per element (7.5x fewer all_to_all bytes than fp32), always through the
+    # decoded block (no rule kernel reads mx4 records; exchanged_packed stays None).  With
+    # wire_seed set (--mx-rounding stochastic) every packed row is rounded stochastically
+    # under its own seed (_row_seed).
     wire = None
+    wire_seed = None  # cfg.seed for stochastic rounding on the mx4 wire; None: nearest
 
     def __init__(self, comm: Communicator, space: FlatSpace, comm_dtype=torch.float32):
         self.comm = comm
@@ -101,6 +107,7 @@ class Aggregator:
         self._works: list = []
         self._started: set = set()
         self._pending_copies: list = []  # (tmp2d, row, slo, shi) from bucket exchanges
+        self._packed_rows = 0  # rows packed on the mx4 wire so far (not checkpointed)
 
     # ---------------------------------------------------------- row exchange
     def _ensure_recv(self, rows: int, device) -> None:
@@ -115,16 +122,27 @@ class Aggregator:
                 self._recv32 = torch.empty(rows, self.comm.world, self.space.shard,
                                            dtype=torch.float32, device=device)
 
-    def _start_row_mx8(self, payload: torch.Tensor, row: int) -> None:
+    def _row_seed(self):
+        """The 64-bit seed of the next stochastically rounded row: cfg.seed in the high word,
+        (rows packed by this aggregator so far) * world + rank in the low one, so no two
+        (worker, step) pairs of a run share a random stream.  None: round to nearest."""
+        if self.wire_seed is None:
+            return None
+        low = self._packed_rows * max(self.comm.world, 1) + self.comm.rank
+        self._packed_rows += 1
+        return (int(self.wire_seed) & 0xFFFFFFFF) << 32 | (low & 0xFFFFFFFF)
+
+    def _start_row_packed(self, payload: torch.Tensor, row: int) -> None:
         rows, world, shard = payload.shape[0], self.comm.world, self.space.shard
+        pack, _, chunk_bytes = _PACKED_WIRES[self.wire]
         if self._send is None or self._send.shape[0] != rows:
-            cb, dev = ops.mx8_chunk_bytes(shard), payload.device
+            cb, dev = chunk_bytes(shard), payload.device
             self._send = torch.empty(rows, world * cb, dtype=torch.uint8, device=dev)
             # one rank: the packed rows are the received block
             self._recv = (torch.empty(rows, world, cb, dtype=torch.uint8, device=dev)
                           if self.comm.distributed else self._send)
             self._recv32 = None  # the decoded block: allocated by the rules that read one
-        ops.mx8_pack(payload[row], self._send[row], shard)
+        pack(payload[row], self._send[row], shard, self._row_seed())
         if self.comm.distributed:
             w = self.comm.all_to_all_row(self._send[row], self._recv[row], async_op=True)
             if w is not None:
@@ -132,8 +150,8 @@ class Aggregator:
         self._started.add(row)
 
     def start_row(self, payload: torch.Tensor, row: int) -> None:
-        if self.wire == "mx8":
-            return self._start_row_mx8(payload, row)
+        if self.wire in _PACKED_WIRES:
+            return self._start_row_packed(payload, row)
         if not self.comm.distributed:
             return
         self._ensure_recv(payload.shape[0], payload.device)
@@ -154,7 +172,7 @@ class Aggregator:
         isends).  Same wire format as start_row, delivered into the same recv slots;
         the trainer calls mark_row_started(row) once every bucket of the row is
         posted."""
-        if not self.comm.distributed or self.wire == "mx8":
+        if not self.comm.distributed or self.wire in _PACKED_WIRES:
             return
         self._ensure_recv(payload.shape[0], payload.device)
         world, shard, rank = self.comm.world, self.space.shard, self.comm.rank
@@ -174,7 +192,7 @@ class Aggregator:
             self._pending_copies.append((tmp.view(world, m), row, mlo - rank * shard, mhi - rank * shard))
 
     def mark_row_started(self, row: int) -> None:
-        if self.wire != "mx8":
+        if self.wire not in _PACKED_WIRES:
             self._started.add(row)
 
     def exchanged(self, payload: torch.Tensor) -> torch.Tensor:
@@ -223,14 +241,14 @@ class Aggregator:
 
     def _exchange(self, payload: torch.Tensor) -> torch.Tensor:
         rows = payload.shape[0]
-        if self.wire == "mx8":
+        if self.wire in _PACKED_WIRES:
             self._start_rest(payload)
             self._drain()
             P = rows * self.comm.world
             if self._recv32 is None or self._recv32.shape[0] != P:
                 self._recv32 = torch.empty(P, self.space.shard, dtype=torch.float32,
                                            device=payload.device)
-            ops.mx8_unpack(self._recv.view(P, -1), self._recv32)
+            _PACKED_WIRES[self.wire][1](self._recv.view(P, -1), self._recv32)
             return self._recv32
         if not self.comm.distributed:
             return payload.view(rows, self.space.shard)
@@ -251,6 +269,15 @@ class Aggregator:
         """The (d_pad,) flat tensor a checkpoint must carry for this rule to resume
         exactly, or None: every rule but centered clipping is memoryless."""
         return None
+
+
+# wire -> (pack op taking (row, out, chunk, seed), unpack op, chunk-bytes function) of the
+# block-scaled wires; mx8 rounds to nearest only and is never given a seed
+_PACKED_WIRES = {
+    "mx8": (lambda g, out, chunk, seed: ops.mx8_pack(g, out, chunk), ops.mx8_unpack,
+            ops.mx8_chunk_bytes),
+    "mx4": (ops.mx4_pack, ops.mx4_unpack, ops.mx4_chunk_bytes),
+}
 
 
 class MeanAggregator(Aggregator):
@@ -1137,15 +1164,15 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
                 f"got mode {cfg.mode!r}, err mode {cfg.err_mode!r}, pre-aggregation "
                 f"{cfg.pre_aggregation!r}")
         return SignMajorityAggregator(comm, space, num_workers=num_workers)
-    mx8 = cfg.compress_grad == "mx8"
-    if cfg.mode == "normal" and (cfg.err_mode in COLLUDING_MODES or nnm or mx8):
+    wire = cfg.compress_grad if cfg.compress_grad in _PACKED_WIRES else None
+    if cfg.mode == "normal" and (cfg.err_mode in COLLUDING_MODES or nnm or wire):
         # MeanAggregator sums inside the reduce-scatter: the honest rows are never
         # visible together, and a sum on the wire cannot carry a quantised format.  Under
-        # a colluding adversary, behind a pre-aggregation and on the mx8 wire the plain
+        # a colluding adversary, behind a pre-aggregation and on the mx8 / mx4 wires the plain
         # mean goes over the exchange path instead: the trimmed mean with nothing trimmed.
         cls, kwargs, name = TrimmedMeanAggregator, {"trim": 0}, "mean"
         why = (f"the colluding err mode {cfg.err_mode!r}" if cfg.err_mode in COLLUDING_MODES
-               else "--pre-aggregation nnm" if nnm else "--compress-grad mx8")
+               else "--pre-aggregation nnm" if nnm else f"--compress-grad {wire}")
         hint = (f" (mode 'normal' under {why} is the "
                 "trim=0 mean over the exchange path, so that kernel's limit of 64 workers "
                 "applies)")
@@ -1159,8 +1186,10 @@ def build_baseline_aggregator(cfg, comm, space, num_workers: int) -> Aggregator:
         raise ValueError(f"{e}{hint}") from None
     if name is not None:
         agg.name = name
-    if mx8:
-        agg.wire = "mx8"  # see Aggregator.wire: the decoded block, or exchanged_packed
+    if wire:
+        agg.wire = wire  # see Aggregator.wire: the decoded block, or exchanged_packed
+        if wire == "mx4" and cfg.mx_rounding == "stochastic":
+            agg.wire_seed = cfg.seed
     if nnm:
         from .mixing import NearestNeighborMixing  # mixing imports this module
 

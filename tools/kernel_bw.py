@@ -601,6 +601,69 @@ def mx8_compare(rounds=3):
         print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
 
 
+def mx4_compare(rounds=3):
+    """The MXFP4 wire beside the MXFP8 one: mx4_pack with nearest and with stochastic rounding
+    and mx8_pack on one 11.2M-element row (4 B read + 0.53 / 1.03 B written per element);
+    mx4_unpack and mx8_unpack on the packed 24 x 11.2M and 64 x 11.2M blocks (0.53 / 1.03 B
+    read + 4 B written).  Each arm's GB/s counts its own bytes; the time is the comparison.
+    One 11.2M row (45 MB + its records) fits the last-level cache, so the pack arms measure
+    a cache-resident row, as in mx8_compare.  The mx4 kernels' results are compared with the
+    fallback's torch statement on the device first; event timing, the arms alternate inside
+    each round; min-max over the rounds per arm."""
+    from draco_amd.ops import fallback as fb
+    d = (11_173_952 + 63) // 64 * 64
+    cb4, cb8 = ops.mx4_chunk_bytes(d), ops.mx8_chunk_bytes(d)
+    times, order = {}, []
+    for rows in (24, 64):
+        x = torch.randn(d, device=DEV) * 1e-2
+        x[::1001] = float("nan")
+        p4 = torch.empty(rows, cb4, dtype=torch.uint8, device=DEV)
+        p8 = torch.empty(rows, cb8, dtype=torch.uint8, device=DEV)
+        ref = torch.empty(cb4, dtype=torch.uint8, device=DEV)
+        for seed in (7, None):
+            ops.mx4_pack(x, p4[0], d, seed)
+            fb.mx4_pack(x, ref, d, seed)
+            assert bool((p4[0] == ref).all()), seed
+        for p in range(rows):
+            ops.mx4_pack(x, p4[p], d)
+            ops.mx8_pack(x, p8[p], d)
+        out = torch.empty(rows, d, device=DEV)
+        ops.mx4_unpack(p4, out)
+        yref = torch.empty(1, d, device=DEV)
+        fb.mx4_unpack(ref.view(1, -1), yref)
+        nan = torch.isnan(yref[0])
+        assert bool((torch.isnan(out[rows - 1]) == nan).all())
+        assert bool((out[rows - 1][~nan] == yref[0][~nan]).all())
+        del ref, yref, nan
+        kw = dict(iters=200, warmup=20)
+        arms = [
+            (f"mx4_unpack ({rows} x 11.2M)", lambda: ops.mx4_unpack(p4, out), rows * (cb4 + 4 * d), kw),
+            (f"mx8_unpack ({rows} x 11.2M)", lambda: ops.mx8_unpack(p8, out), rows * (cb8 + 4 * d), kw),
+        ]
+        if rows == 24:
+            kw = dict(iters=2000, warmup=100)
+            arms += [
+                ("mx4_pack nearest (one 11.2M row)", lambda: ops.mx4_pack(x, p4[0], d), 4 * d + cb4, kw),
+                ("mx4_pack stochastic (one 11.2M row)", lambda: ops.mx4_pack(x, p4[0], d, 7),
+                 4 * d + cb4, kw),
+                ("mx8_pack (one 11.2M row)", lambda: ops.mx8_pack(x, p8[0], d), 4 * d + cb8, kw),
+            ]
+        for r in range(rounds):
+            print(f"# round {r}")
+            for name, fn, nbytes, akw in arms:
+                ms = ev_ms(fn, **akw)
+                if name not in times:
+                    times[name] = []
+                    order.append((name, nbytes))
+                times[name].append(ms)
+                report(name, ms, nbytes)
+        del x, p4, p8, out
+    print("# min - max over rounds, GB/s at the min")
+    for name, nbytes in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
+
+
 def mx8_fused_compare(rounds=3):
     """The rules that decode the MXFP8 records in their own kernel (ops.mx8_column_trimmed_mean
     / ops.mx8_column_mean_around) beside the two-launch route they replace (mx8_unpack into a
@@ -868,6 +931,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("MX8_FUSED_ONLY") == "1":
         mx8_fused_compare()
+        raise SystemExit(0)
+    if os.environ.get("MX4_ONLY") == "1":
+        mx4_compare()
         raise SystemExit(0)
     if os.environ.get("MX8_ONLY") == "1":
         mx8_compare()
