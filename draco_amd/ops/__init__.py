@@ -26,6 +26,8 @@ __all__ = [
     "mx8_chunk_bytes",
     "mx8_column_trimmed_mean",
     "mx8_column_mean_around",
+    "mx8_clip_step_",
+    "mx8_weiszfeld_step",
     "mx8_segment_gram",
     "mx8_segment_mean_around",
     "mx4_pack",
@@ -239,6 +241,32 @@ def mx8_column_mean_around(packed, keep, clo, chi, out):
         ext.mx8_column_mean_around(packed, int(keep), int(clo), int(chi), out)
         return
     fallback.mx8_column_mean_around(packed, int(keep), int(clo), int(chi), out)
+
+
+def mx8_clip_step_(packed, v, w, dist=True):
+    """clip_step_(mx8_unpack(packed), v, w, dist) for packed (P, mx8_chunk_bytes(chunk)) uint8,
+    1 <= P <= 64, v (chunk,) fp32 updated in place, w (P,) fp32, without the fp32 block: on
+    the GPU one kernel reads the records (k_mx8_clip_step).  v is bit for bit clip_step_'s on
+    the decoded block; d2 (P,), or None with dist=False, is within its rounding bound and
+    repeatable bit for bit.  Definition and checks: fallback.mx8_clip_step_."""
+    ext = _native_for(packed)
+    if ext is not None:
+        return ext.mx8_clip_step(packed, v, w, bool(dist))
+    return fallback.mx8_clip_step_(packed, v, w, dist)
+
+
+def mx8_weiszfeld_step(packed, w, seg, z, dist=True):
+    """One Weiszfeld iteration on packed (P, mx8_chunk_bytes(chunk)) uint8, 1 <= P <= 64, in
+    one pass: with w (P, L) fp32 given, z (chunk,) becomes segment_weighted_mean(
+    mx8_unpack(packed), w, seg, z), bit for bit (columns outside every segment untouched);
+    with w None z is only read.  Returns segment_sqdist(mx8_unpack(packed), z, seg) at the NEW
+    z, (P, L) fp32, or None with dist=False.  seg: (L+1,) local bounds, searched on the device.
+    The distances end in float atomics: their last bits may differ between two runs, z's do
+    not.  Definition and checks: fallback.mx8_weiszfeld_step."""
+    ext = _native_for(packed)
+    if ext is not None:
+        return ext.mx8_weiszfeld_step(packed, w, seg.to(packed.device), z, bool(dist))
+    return fallback.mx8_weiszfeld_step(packed, w, seg, z, dist)
 
 
 def mx8_segment_gram(packed, seg):

@@ -21,6 +21,8 @@
 // the column sort on that wire: it reads the packed records, four columns per lane.
 // k_mx8_seg_gram / k_mx8_seg_mean_around are Multi-Krum's and Bulyan's two steps on it: the
 // Gram decodes a lane's MX block in registers and multiplies on the matrix unit.
+// k_mx8_clip_step / k_mx8_weiszfeld are the iterative rules' passes (centered clipping, the
+// geometric median) on it: codes packed in registers, each row decoded twice per pass.
 // k_mx4_pack / k_mx4_unpack (the MXFP4 4-bit wire) use the scaled FP4 converts; a block is
 // one quad of lanes, and the stochastic rounding is integer VALU work on a stateless hash.
 //
@@ -2179,6 +2181,383 @@ void mx8_column_mean_around(torch::Tensor packed, long keep, long clo, long chi,
                        (float)keep);
 }
 
+// --------------------------------------------------------------------------- mx8 iterative rules
+// Centered clipping and the geometric median on the mx8 wire.  Both rules pass over the
+// received block several times per step (iters + 1 and n_iter + 1 passes), and each pass
+// holds one column of all P rows in registers, moves a centre and returns every row's
+// squared distance to the new centre.  mx8_clip_step_ = clip_step_(mx8_unpack(.), ..) and
+// mx8_weiszfeld_step = segment_weighted_mean(mx8_unpack(.), ..) followed by segment_sqdist
+// at the new centre, in ONE pass over the packed records: ~1.03 B per row and column per
+// pass instead of 4 B (8 B for the two Weiszfeld kernels), and no fp32 block anywhere.
+//
+// Shared by the two kernels: k_mx8_col's access (a wave walks units of 256 columns, a lane
+// owns four adjacent columns: per row one dword of codes and its block's scale byte, all P
+// code loads and all P scale loads issued before the first convert) and its registers (the
+// codes stay packed, N dwords; a row's scale byte becomes the fp32 operand
+// 2^(max(s,10)-127) in place and a NaN block is folded into the codes).  Every row is
+// decoded TWICE from those registers, two columns per v_cvt_scalef32_pk_f32_fp8: once for
+// the update of the centre and once for the distances to the updated centre, so no decoded
+// column is kept: N codes + N scales + N distance accumulators, four columns per lane at
+// every padded size (k_clip_step drops to two at N = 48 / 64).  No instantiation uses
+// scratch (profiles/kernel_bw_mx8_iter.txt has the register counts).
+template <int N>
+__device__ __forceinline__ void mx8_fold_scales(unsigned (&codes)[N], unsigned (&sc)[N]) {
+#pragma unroll
+  for (int p = 0; p < N; ++p) {
+    bool nan_block = sc[p] == 0xffu;
+    codes[p] = nan_block ? 0x7f7f7f7fu : codes[p];
+    sc[p] = (nan_block ? 127u : max(sc[p], 10u)) << 23;
+  }
+}
+
+// One dword of codes and the block's scale byte per row, for the rows `want` names: the
+// record of row p starts p * cb bytes into `packed` and every offset is 32-bit (the block is
+// below 4 GiB, checked on the host), so the loads share ONE 64-bit base and a row costs a
+// 32-bit add, not a base pointer of its own held across the kernel.
+template <int N, typename Want>
+__device__ __forceinline__ void mx8_load_rows(const unsigned char *__restrict__ packed, unsigned cb,
+                                              unsigned o, unsigned so, unsigned (&codes)[N],
+                                              unsigned (&sc)[N], Want want) {
+  unsigned ro = 0u;
+#pragma unroll
+  for (int p = 0; p < N; ++p) {
+    codes[p] = 0u;
+    sc[p] = 127u;
+    if (want(p)) {
+      codes[p] = *reinterpret_cast<const unsigned *>(packed + (size_t)(ro + o));
+      sc[p] = packed[(size_t)(ro + so)];
+    }
+    ro += cb;
+  }
+}
+
+// the lane's four columns of one row
+__device__ __forceinline__ float4 mx8_row4(unsigned codes, unsigned scale) {
+  mx8_v2f a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes, __uint_as_float(scale), false);
+  mx8_v2f b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes, __uint_as_float(scale), true);
+  return make_float4(a.x, a.y, b.x, b.y);
+}
+
+// Before a row's second decode: an empty asm makes the codes opaque, so that the compiler
+// converts them again instead of keeping the first decode's 4 N floats alive across the
+// update (it did: 149 registers at N = 24 against 3 N of codes, scales and accumulators).
+__device__ __forceinline__ void mx8_decode_again(unsigned &codes) { asm volatile("" : "+v"(codes)); }
+
+__device__ __forceinline__ float sumsq_to(float4 x, float4 c) {
+  float dx = x.x - c.x, dy = x.y - c.y, dz = x.z - c.z, dw = x.w - c.w;
+  return dx * dx + dy * dy + dz * dz + dw * dw;
+}
+
+// k_mx8_clip_step: k_clip_step's arithmetic, unchanged, on the records.  w is wave-uniform:
+// the row tests are scalar branches, a row with w[p] == 0 is never used by the update (and
+// not loaded at all when !DIST), so its NaNs cannot reach v; with every weight zero v is not
+// written.  Per column the terms enter in ascending row order, as there: v comes out bit
+// for bit as from k_clip_step on the decoded block.  The distances take k_clip_step's
+// route, no float atomics: lane accumulators over the lane's units, xor butterfly over the
+// wave, the block's waves in ascending order through LDS, one row of the (gridDim, P)
+// workspace per block, k_clip_finish.  The grid depends on chunk alone, so two runs agree
+// bit for bit; the sum order is not k_clip_step's at N = 48 / 64 (four columns per lane
+// here), so d2 agrees with it within the rounding bound only.
+template <int N, bool DIST>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_clip_step(const unsigned char *__restrict__ packed, float4 *__restrict__ v,
+                const float *__restrict__ w, float *__restrict__ ws, int P, unsigned chunk,
+                unsigned cbytes, int units) {
+  __shared__ float part[NTHREADS / WAVE][N];
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const int ustride = gridDim.x * (NTHREADS / WAVE);
+  float wr[N];
+  bool any = false;
+#pragma unroll
+  for (int p = 0; p < N; ++p) {
+    wr[p] = p < P ? w[p] : 0.f;
+    any = any || wr[p] != 0.f;
+  }
+  float acc[N];
+#pragma unroll
+  for (int p = 0; p < N; ++p) acc[p] = 0.f;
+  for (int u = blockIdx.x * (NTHREADS / WAVE) + wave; u < units; u += ustride) {
+    const unsigned o = (unsigned)u * 256u + 4u * lane;  // the lane's first column
+    if (o >= chunk) continue;  // no cross-lane step inside the loop
+    const unsigned so = chunk + o / 32;
+    unsigned codes[N], sc[N];
+    mx8_load_rows(packed, cbytes, o, so, codes, sc,
+                  [&](int p) { return p < P && (DIST || wr[p] != 0.f); });
+    float4 vv = v[o / 4];
+    mx8_fold_scales(codes, sc);
+    float4 delta = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      if (wr[p] != 0.f) {  // wr[p] == 0 for p >= P
+        float4 x = mx8_row4(codes[p], sc[p]);
+        delta.x = fmaf(wr[p], x.x - vv.x, delta.x);
+        delta.y = fmaf(wr[p], x.y - vv.y, delta.y);
+        delta.z = fmaf(wr[p], x.z - vv.z, delta.z);
+        delta.w = fmaf(wr[p], x.w - vv.w, delta.w);
+      }
+    }
+    if (any) {
+      vv = make_float4(vv.x + delta.x, vv.y + delta.y, vv.z + delta.z, vv.w + delta.w);
+      v[o / 4] = vv;
+    }
+    if (DIST) {
+#pragma unroll
+      for (int p = 0; p < N; ++p) {
+        if (p < P) {
+          mx8_decode_again(codes[p]);
+          acc[p] += sumsq_to(mx8_row4(codes[p], sc[p]), vv);
+        }
+      }
+    }
+  }
+  if (DIST) {
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      if (p < P) {
+        float a = acc[p];
+#pragma unroll
+        for (int o = WAVE / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, WAVE);
+        if (lane == 0) part[wave][p] = a;
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < P) {
+      float a = part[0][threadIdx.x];
+#pragma unroll
+      for (int k = 1; k < NTHREADS / WAVE; ++k) a += part[k][threadIdx.x];
+      ws[blockIdx.x * (long)P + threadIdx.x] = a;
+    }
+  }
+}
+
+// check_mx8_col's checks for the two ops, and the 32-bit byte offsets of mx8_load_rows
+static inline int check_mx8_iter(const char *op, const torch::Tensor &packed,
+                                 const torch::Tensor &vz) {
+  TORCH_CHECK(vz.dim() == 1, op, ": the centre must be 1D");
+  int units = check_mx8_col(op, packed, vz);
+  TORCH_CHECK(packed.numel() <= 0xffffffffL, op, ": ", packed.numel(),
+              " bytes of records exceed the 32-bit byte offset");
+  return units;
+}
+
+c10::optional<torch::Tensor> mx8_clip_step(torch::Tensor packed, torch::Tensor v, torch::Tensor w,
+                                           bool dist) {
+  const char *op = "mx8_clip_step";
+  int units = check_mx8_iter(op, packed, v);
+  long P = packed.size(0), chunk = v.numel();
+  const unsigned cb = (unsigned)mx8_chunk_bytes(chunk);
+  CHECK_IN(w);
+  TORCH_CHECK(w.scalar_type() == torch::kFloat32 && w.dim() == 1 && w.size(0) == P, op,
+              ": w must be fp32 of shape (", P, ",)");
+  TORCH_CHECK(w.device() == packed.device(), op, ": w must be on packed's device");
+  c10::optional<torch::Tensor> out;
+  if (dist) out = torch::zeros({P}, v.options());
+  if (units == 0) return out;  // chunk = 0: no launch
+  const unsigned char *pp = packed.data_ptr<uint8_t>();
+  float4 *vp = (float4 *)v.data_ptr<float>();
+  const float *wp = w.data_ptr<float>();
+  int nb = n_blocks(units, NTHREADS / WAVE);
+  for_padded(P, [&](auto n_pad) {
+    constexpr int N = decltype(n_pad)::value;
+    if (dist) {
+      torch::Tensor ws = torch::empty({(long)nb, P}, v.options());
+      launch(k_mx8_clip_step<N, true>, dim3(nb), 0, pp, vp, wp, ws.data_ptr<float>(), (int)P,
+             (unsigned)chunk, cb, units);
+      launch(k_clip_finish, dim3((int)P), 0, ws.data_ptr<float>(), out->data_ptr<float>(), nb,
+             (int)P);
+    } else {
+      launch(k_mx8_clip_step<N, false>, dim3(nb), 0, pp, vp, wp, nullptr, (int)P, (unsigned)chunk,
+             cb, units);
+    }
+  });
+  return out;
+}
+
+// k_mx8_weiszfeld: one Weiszfeld iteration of the per-segment geometric median in one pass:
+// UPD: z[j] = fmaf(w[P-1, l], x[P-1, j], .. fmaf(w[0, l], x[0, j], 0)) for every column j of
+// a segment l (k_seg_wmean's chain, ascending p, no zero-weight skip: fmaf(0, NaN) is NaN);
+// columns outside every segment are left untouched; !UPD: z is only read.  DIST:
+// part[p, l] += sum over the segment's columns of (x[p, j] - z_new[j])^2 (k_seg_sqdist at
+// the new centre).
+//
+// Work split.  Unlike the grid-stride kernels of this file a WAVE OWNS A CONTIGUOUS RUN of
+// `upw` units (and so does a block), so it stays inside one segment for long stretches.  The
+// bounds are staged in LDS and searched on the device; per unit the search is wave-uniform.
+//   Fast path, the unit's 256 columns inside one segment: the P weights are wave-uniform
+// loads, the P distance accumulators stay in registers across units and are flushed (wave
+// tree, one LDS add per row) only when the wave's segment changes or its run ends.
+//   Slow path, a unit that holds a bound, a gap or the tail of the record: one column at a
+// time with the column's own segment, weights fetched per column, columns outside every
+// segment masked out of z and of the distances, one LDS add per (row, column).  At most
+// one unit per bound: it need not be fast.
+// The block's (P, L) LDS partials go to `part` with at most one global float atomic per
+// (block, segment, row), as k_seg_sqdist and k_mx8_seg_gram do: the order of those sums, and
+// so the last bits of the distances, may differ between two runs.  z takes no part in any
+// cross-lane step and is bit-repeatable, and bit for bit k_seg_wmean's on the decoded block.
+// Whatever seg holds, no access leaves the record: every lane is held to o < chunk and the
+// segment index to [0, L).
+template <int N, bool UPD, bool DIST>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx8_weiszfeld(const unsigned char *__restrict__ packed, const float *__restrict__ w,
+                const long *__restrict__ seg, int L, int P, float *__restrict__ z,
+                float *__restrict__ part /* (P, L), zeroed */, unsigned chunk, unsigned cbytes,
+                int units, int upw) {
+  extern __shared__ char smem[];
+  long *s_seg = (long *)smem;
+  float *s_acc = (float *)(smem + (L + 1) * sizeof(long));  // (P, L)
+  stage_segments(s_seg, seg, L);
+  if (DIST)
+    for (int i = threadIdx.x; i < P * L; i += blockDim.x) s_acc[i] = 0.f;
+  __syncthreads();
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const long g = blockIdx.x * (long)(NTHREADS / WAVE) + wave;
+  const int u0 = (int)min(g * upw, (long)units), u1 = (int)min((g + 1) * upw, (long)units);
+  float acc[N];
+#pragma unroll
+  for (int p = 0; p < N; ++p) acc[p] = 0.f;
+  int cur_l = -1;  // the segment the register accumulators belong to
+
+  auto flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      if (p < P) {
+        float a = wave_reduce_sum(acc[p]);
+        if (lane == 0) atomicAdd(&s_acc[p * L + cur_l], a);
+        acc[p] = 0.f;
+      }
+    }
+  };
+
+  for (int u = u0; u < u1; ++u) {  // wave-uniform
+    const unsigned c0 = (unsigned)u * 256u, o = c0 + 4u * lane;
+    const bool in = o < chunk;
+    const unsigned so = chunk + o / 32;
+    unsigned codes[N], sc[N];
+    mx8_load_rows(packed, cbytes, o, so, codes, sc, [&](int p) { return p < P && in; });
+    int l = cur_l;
+    if (l < 0 || (long)c0 < s_seg[l] || (long)c0 + 256 > s_seg[l + 1])
+      l = __builtin_amdgcn_readfirstlane(find_segment(s_seg, L, (long)c0));
+    const bool whole = __builtin_amdgcn_readfirstlane(
+        (int)((long)c0 >= s_seg[l] && (long)c0 + 256 <= s_seg[l + 1] && c0 + 256u <= chunk));
+    mx8_fold_scales(codes, sc);
+    if (whole) {
+      if (l != cur_l) {
+        if (DIST && cur_l >= 0) flush();
+        cur_l = l;
+      }
+      float4 zz;
+      if (UPD) {
+        float wr[N];
+#pragma unroll
+        for (int p = 0; p < N; ++p) wr[p] = p < P ? w[p * L + l] : 0.f;
+        zz = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int p = 0; p < N; ++p) {
+          if (p < P) {
+            float4 x = mx8_row4(codes[p], sc[p]);
+            zz.x = fmaf(wr[p], x.x, zz.x);
+            zz.y = fmaf(wr[p], x.y, zz.y);
+            zz.z = fmaf(wr[p], x.z, zz.z);
+            zz.w = fmaf(wr[p], x.w, zz.w);
+          }
+        }
+        *reinterpret_cast<float4 *>(z + o) = zz;
+      } else {
+        zz = *reinterpret_cast<const float4 *>(z + o);
+      }
+      if (DIST) {
+#pragma unroll
+        for (int p = 0; p < N; ++p) {
+          if (p < P) {
+            mx8_decode_again(codes[p]);
+            acc[p] += sumsq_to(mx8_row4(codes[p], sc[p]), zz);
+          }
+        }
+      }
+    } else {
+#pragma unroll 1
+      for (int k = 0; k < 4; ++k) {
+        const long col = (long)o + k;
+        const bool valid = in && in_segments(s_seg, L, col);
+        const int lc = valid ? find_segment(s_seg, L, col) : 0;
+        float zc = 0.f;
+        if (UPD) {
+#pragma unroll
+          for (int p = 0; p < N; ++p) {
+            if (p < P) {
+              mx8_v2f x = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes[p] >> (8 * k),
+                                                                   __uint_as_float(sc[p]), false);
+              zc = fmaf(w[p * L + lc], x.x, zc);
+            }
+          }
+          if (valid) z[col] = zc;
+        } else if (valid) {
+          zc = z[col];
+        }
+        if (DIST) {
+#pragma unroll
+          for (int p = 0; p < N; ++p) {
+            if (p < P) {
+              mx8_v2f x = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(codes[p] >> (8 * k),
+                                                                   __uint_as_float(sc[p]), false);
+              float dlt = x.x - zc;
+              if (valid) atomicAdd(&s_acc[p * L + lc], dlt * dlt);
+            }
+          }
+        }
+      }
+    }
+  }
+  if (DIST) {
+    if (cur_l >= 0) flush();
+    __syncthreads();
+    for (int i = threadIdx.x; i < P * L; i += blockDim.x)
+      if (s_acc[i] != 0.f) atomicAdd(&part[i], s_acc[i]);
+  }
+}
+
+// units per wave of k_mx8_weiszfeld: the runs grow once 1024 blocks of four waves are out
+static inline int mx8_weiszfeld_run(int units) { return (units + 4095) / 4096; }
+
+c10::optional<torch::Tensor> mx8_weiszfeld_step(torch::Tensor packed,
+                                                c10::optional<torch::Tensor> w, torch::Tensor seg,
+                                                torch::Tensor z, bool dist) {
+  const char *op = "mx8_weiszfeld_step";
+  int units = check_mx8_iter(op, packed, z);
+  long P = packed.size(0), chunk = z.numel();
+  SegmentLds sl = segment_lds(op, seg, (size_t)P * sizeof(float));
+  TORCH_CHECK(seg.device() == packed.device(), op, ": seg must be on packed's device");
+  const float *wp = nullptr;
+  if (w.has_value()) {
+    CHECK_IN((*w));
+    TORCH_CHECK(w->scalar_type() == torch::kFloat32 && w->dim() == 2 && w->size(0) == P &&
+                    w->size(1) == sl.L, op, ": w must be fp32 of shape (", P, ", ", sl.L, ")");
+    TORCH_CHECK(w->device() == packed.device(), op, ": w must be on packed's device");
+    wp = w->data_ptr<float>();
+  }
+  c10::optional<torch::Tensor> out;
+  if (dist) out = torch::zeros({P, (long)sl.L}, z.options());
+  if (units == 0 || sl.L == 0 || (!wp && !dist)) return out;  // nothing to do: no launch
+  const unsigned char *pp = packed.data_ptr<uint8_t>();
+  float *zp = z.data_ptr<float>(), *op_ = dist ? out->data_ptr<float>() : nullptr;
+  const long *sp = seg.data_ptr<long>();
+  int upw = mx8_weiszfeld_run(units);
+  dim3 grid((units + upw * (NTHREADS / WAVE) - 1) / (upw * (NTHREADS / WAVE)));
+  for_padded(P, [&](auto n_pad) {
+    constexpr int N = decltype(n_pad)::value;
+    auto go = [&](auto kernel) {
+      launch(kernel, grid, sl.bytes, pp, wp, sp, sl.L, (int)P, zp, op_, (unsigned)chunk,
+             (unsigned)mx8_chunk_bytes(chunk), units, upw);
+    };
+    if (wp && dist) go(k_mx8_weiszfeld<N, true, true>);
+    else if (wp) go(k_mx8_weiszfeld<N, true, false>);
+    else go(k_mx8_weiszfeld<N, false, true>);
+  });
+  return out;
+}
+
 // --------------------------------------------------------------------------- mx8 krum rules
 // Multi-Krum and Bulyan on the mx8 wire: mx8_segment_gram = segment_gram(mx8_unpack(.)) and
 // mx8_segment_mean_around = segment_mean_around(mx8_unpack(.), ..), both from the packed
@@ -2840,6 +3219,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx8_unpack", &mx8_unpack);
   m.def("mx8_column_trimmed_mean", &mx8_column_trimmed_mean);
   m.def("mx8_column_mean_around", &mx8_column_mean_around);
+  m.def("mx8_clip_step", &mx8_clip_step);
+  m.def("mx8_weiszfeld_step", &mx8_weiszfeld_step);
   m.def("mx8_segment_gram", &mx8_segment_gram);
   m.def("mx8_segment_mean_around", &mx8_segment_mean_around);
   m.def("mx4_pack", &mx4_pack);

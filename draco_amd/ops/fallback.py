@@ -875,6 +875,37 @@ def mx8_column_mean_around(packed: torch.Tensor, keep: int, clo: int, chi: int,
     column_mean_around(x, keep, clo, chi, out.view(-1))
 
 
+# --------------------------------------------------------------------- mx8 iterative rules
+@torch.no_grad()
+def mx8_clip_step_(packed: torch.Tensor, v: torch.Tensor, w: torch.Tensor, dist: bool = True):
+    """clip_step_ on the decoded rows of packed (P, mx8_chunk_bytes(chunk)) uint8, 1 <= P <=
+    64, v (chunk,) fp32 in place: by definition mx8_unpack into a temporary, then clip_step_.
+    The HIP kernel reads the records and gives clip_step's v bit for bit."""
+    if v.dim() != 1:
+        raise ValueError(f"mx8_clip_step_: v must be 1D, got {v.dim()}D")
+    x = _mx8_decoded("mx8_clip_step_", packed, v)
+    return clip_step_(x, v, w, dist)
+
+
+@torch.no_grad()
+def mx8_weiszfeld_step(packed: torch.Tensor, w, seg: torch.Tensor, z: torch.Tensor,
+                       dist: bool = True):
+    """One Weiszfeld iteration on the decoded rows of packed (P, mx8_chunk_bytes(chunk)) uint8,
+    1 <= P <= 64: by definition mx8_unpack into a temporary, then segment_weighted_mean into z
+    (chunk,) with the weights w (P, L) (w None: z is left as it is), then segment_sqdist at
+    that z: (P, L), or None with dist=False."""
+    if z.dim() != 1:
+        raise ValueError(f"mx8_weiszfeld_step: z must be 1D, got {z.dim()}D")
+    x = _mx8_decoded("mx8_weiszfeld_step", packed, z)
+    P, L = x.shape[0], seg.numel() - 1
+    if w is not None:
+        if w.dtype != torch.float32 or tuple(w.shape) != (P, L):
+            raise ValueError(f"mx8_weiszfeld_step: w must be fp32 of shape ({P}, {L}), got "
+                             f"{w.dtype} {tuple(w.shape)}")
+        segment_weighted_mean(x, w, seg, z)
+    return segment_sqdist(x, z, seg) if dist else None
+
+
 # --------------------------------------------------------------------- segment mean around
 @torch.no_grad()
 def segment_mean_around(x: torch.Tensor, sel: torch.Tensor, seg: torch.Tensor, keep: int,

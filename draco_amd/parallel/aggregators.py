@@ -80,10 +80,11 @@ class Aggregator:
     # uint8 send buffer and posts its all_to_all into a (rows, world, chunk_bytes) receive
     # buffer; _exchange drains and decodes with ONE kernel into a persistent (rows * world,
     # shard) fp32 block, which collusion, mixing and every rule read as they read the fp32
-    # exchange.  The per-coordinate rules (median, trimmed_mean, mean, meamed, phocas) and
-    # multi_krum / bulyan with
+    # exchange.  The per-coordinate rules (median, trimmed_mean, mean, meamed, phocas),
+    # multi_krum / bulyan, and geometric_median (up to 64 rows) / centered_clip with
     # no collusion and no mixing skip that block: exchanged_packed hands them the received
-    # bytes and their kernels decode while they load.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
+    # bytes and their kernels decode while they load; krum alone still reads the decoded
+    # block.  Any bytes decode to fp32 values, NaN or +-Inf, and a non-finite element
     # stays non-finite.  With one rank the rows are still packed and unpacked.  The
     # bucketed path is not built for this wire: the row ships whole from aggregate().
     # "mx4" (--compress-grad mx4) takes the same route with ops.mx4_pack / ops.mx4_unpack: one
@@ -213,8 +214,8 @@ class Aggregator:
         """On the mx8 wire with no collusion and no mixing attached: the drained exchange
         as it travelled, (rows*world, chunk_bytes) uint8 in exchanged()'s row order, for the
         rules whose kernel decodes it itself (ops.mx8_column_trimmed_mean /
-        ops.mx8_column_mean_around, ops.mx8_segment_gram / ops.mx8_segment_mean_around); the
-        fp32 block is then never allocated.  None
+        ops.mx8_column_mean_around, ops.mx8_segment_gram / ops.mx8_segment_mean_around,
+        ops.mx8_weiszfeld_step, ops.mx8_clip_step_); the fp32 block is then never allocated.  None
         otherwise (nothing is exchanged yet): the caller goes on to exchanged()."""
         if self.wire != "mx8" or self.collusion is not None or self.mixing is not None:
             return None
@@ -222,6 +223,15 @@ class Aggregator:
         self._drain()
         # (rows, world, cb) is row l*world + src already; one rank: _recv is _send, (rows, cb)
         return self._recv.view(payload.shape[0] * self.comm.world, -1)
+
+    def exchanged_packed_iter(self, payload: torch.Tensor):
+        """exchanged_packed for the rules that pass over the records several times per step
+        (ops.mx8_weiszfeld_step, ops.mx8_clip_step_): their kernels hold at most 64 rows and
+        address the records with 32-bit byte offsets.  None beyond either limit as well."""
+        P = payload.shape[0] * self.comm.world
+        if P > 64 or P * ops.mx8_chunk_bytes(self.space.shard) >= 2 ** 32:
+            return None
+        return self.exchanged_packed(payload)
 
     def _check_rows(self, P: int) -> None:
         if self.MAX_WORKERS is not None and P > self.MAX_WORKERS:
@@ -513,7 +523,42 @@ class GeoMedianAggregator(Aggregator):
         # P <= 64 points, and the CPU early-exit lane cross-checks the fixpoint).
         self.gpu_iters = gpu_iters
 
+    def _converged(self, z: torch.Tensor, z_prev: torch.Tensor) -> bool:
+        stats = torch.stack([(z - z_prev).pow(2).sum(), z.pow(2).sum()])
+        self.comm.all_reduce(stats)
+        d_val, s_val = float(stats[0]), float(stats[1])
+        return bool(np.isfinite(d_val) and d_val <= self.tol * self.tol * max(s_val, 1e-12))
+
+    def _aggregate_packed(self, packed: torch.Tensor) -> torch.Tensor:
+        """The same iteration on the mx8 records, n_iter + 1 passes of ONE kernel
+        (ops.mx8_weiszfeld_step updates z and returns the distances to the new z) instead of
+        the mean and 2 * n_iter passes over a decoded block that is never allocated here.
+        The first pass is the mean as the update with uniform weights, sum (1/P) x and not
+        (sum x) / P: it can differ from recv.mean(0) in the last bit, and the iteration's
+        fixpoint does not depend on where it starts."""
+        P, L = packed.shape[0], self.local_seg.numel() - 1
+        on_gpu = packed.is_cuda
+        n_iter = self.gpu_iters if on_gpu else self.max_iter
+        # zeros: columns outside every segment (the pad tail) are never written
+        z_new = torch.zeros(self.space.shard, dtype=torch.float32, device=packed.device)
+        z = torch.zeros_like(z_new)
+        w = torch.full((P, L), 1.0 / P, dtype=torch.float32, device=packed.device)
+        part = ops.mx8_weiszfeld_step(packed, w, self.local_seg, z)
+        for it in range(n_iter):
+            self.comm.all_reduce(part)
+            w = 1.0 / part.clamp_min(1e-24).sqrt()
+            w = w / w.sum(dim=0, keepdim=True)
+            part = ops.mx8_weiszfeld_step(packed, w, self.local_seg, z_new, dist=it < n_iter - 1)
+            z, z_new = z_new, z
+            if not on_gpu and ((it & 7) == 7 or it == n_iter - 1) and self._converged(z, z_new):
+                break
+        self.comm.all_gather_shard(z, self._out)
+        return self._out
+
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
+        packed = self.exchanged_packed_iter(payload)  # (P, chunk_bytes), or None
+        if packed is not None:
+            return self._aggregate_packed(packed)
         recv = self.exchanged(payload)  # (P, shard)
         P = recv.shape[0]
         on_gpu = recv.is_cuda
@@ -532,12 +577,8 @@ class GeoMedianAggregator(Aggregator):
             z, z_new = z_new, z
             # convergence check every 8 iterations (CPU lane only: one fused 2-word
             # allreduce + host sync instead of three per iteration)
-            if not on_gpu and ((it & 7) == 7 or it == n_iter - 1):
-                stats = torch.stack([(z - z_new).pow(2).sum(), z.pow(2).sum()])
-                self.comm.all_reduce(stats)
-                d_val, s_val = float(stats[0]), float(stats[1])
-                if np.isfinite(d_val) and d_val <= self.tol * self.tol * max(s_val, 1e-12):
-                    break
+            if not on_gpu and ((it & 7) == 7 or it == n_iter - 1) and self._converged(z, z_new):
+                break
         self.comm.all_gather_shard(z, self._out)
         return self._out
 
@@ -911,7 +952,8 @@ class CenteredClipAggregator(Aggregator):
 
     Shape: all_to_all, then iters + 1 passes of ONE kernel over the local shard
     (ops.clip_step_ applies a clipped step and returns every row's squared distance to
-    the new centre; the first pass has zero weights and only measures) with one
+    the new centre; the first pass has zero weights and only measures; on the mx8 wire
+    ops.mx8_clip_step_ does the same from the packed records) with one
     allreduce of P floats between them, all_gather.  The P-element clip arithmetic is
     fp64 torch on device; nothing is read on the host.  last_weights keeps the last
     iteration's clip factors c_i in [0, 1], on device.
@@ -955,13 +997,18 @@ class CenteredClipAggregator(Aggregator):
         return self._out
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
-        recv = self.exchanged(payload)  # (P, shard)
-        P = recv.shape[0]  # per call: the survivor world is rebuilt, but this reaches the kernel
+        # per call: the survivor world is rebuilt, but this reaches the kernel
+        P = payload.shape[0] * self.comm.world
         self._check_rows(P)
+        # the same passes on the mx8 records, (P, chunk_bytes), with no decoded block, or on
+        # the exchanged (P, shard) block
+        recv, clip_step = self.exchanged_packed_iter(payload), ops.mx8_clip_step_
+        if recv is None:
+            recv, clip_step = self.exchanged(payload), ops.clip_step_
         v = self._shard_out
         v.copy_(self.space.shard_of(self._out, self.comm.rank))
         inf = float("inf")
-        d2 = ops.clip_step_(recv, v, torch.zeros(P, dtype=torch.float32, device=recv.device))
+        d2 = clip_step(recv, v, torch.zeros(P, dtype=torch.float32, device=recv.device))
         tau = self.tau
         for it in range(1, self.iters + 1):
             self.comm.all_reduce(d2)
@@ -972,7 +1019,7 @@ class CenteredClipAggregator(Aggregator):
             # min(1, tau / d) without the 0/0 and inf/inf of the quotient
             c = torch.where(d <= tau, torch.ones_like(d), tau / d)
             c = torch.where(torch.isfinite(d), c, torch.zeros_like(d))
-            d2 = ops.clip_step_(recv, v, (c / P).float(), dist=it < self.iters)
+            d2 = clip_step(recv, v, (c / P).float(), dist=it < self.iters)
         self.last_weights = c
         self.comm.all_gather_shard(v, self._out)
         return self._out

@@ -790,6 +790,102 @@ def mx8_gram_compare(rounds=3):
         print(f"{name:52} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def mx8_iter_compare(rounds=3, n_iter=24, clip_iters=3):
+    """Geometric median and centered clipping on the mx8 wire, kernels only (single GPU, no
+    allreduce): the packed route (n_iter + 1 ops.mx8_weiszfeld_step passes; clip_iters + 1
+    ops.mx8_clip_step_ passes) beside the route it replaces (mx8_unpack into a (P, d) fp32
+    block, then mean(0) + n_iter x (segment_sqdist + segment_weighted_mean); clip_iters + 1
+    clip_step_), at 24 x 11.2M and 64 x 11.2M over ResNet-18's own 62 parameter tensors as
+    segments, with the aggregators' own weight arithmetic between the passes in both routes.
+    The two routes' results are compared first.  Event timing around whole routes, the arms
+    alternate inside each round; min-max over the rounds per arm."""
+    from draco_amd.models import build_model
+    sizes = [p.numel() for p in build_model("ResNet18", "Cifar10").parameters()]
+    seg_host = [0]
+    for n in sizes:
+        seg_host.append(seg_host[-1] + n)
+    d = (seg_host[-1] + 63) // 64 * 64
+    seg = torch.tensor(seg_host, dtype=torch.int64, device=DEV)
+    cb, L = ops.mx8_chunk_bytes(d), len(sizes)
+    print(f"# d = {d}, {L} segments, lengths {min(sizes)} .. {max(sizes)}")
+
+    def weights(part):
+        w = 1.0 / part.clamp_min(1e-24).sqrt()
+        return w / w.sum(dim=0, keepdim=True)
+
+    def factors(d2, P):
+        dd = d2.double().sqrt()
+        tau = torch.kthvalue(dd, (P + 1) // 2).values
+        return (torch.where(dd <= tau, torch.ones_like(dd), tau / dd) / P).float()
+
+    times, order, arms = {}, [], []
+    for P in (24, 64):
+        packed = torch.empty(P, cb, dtype=torch.uint8, device=DEV)
+        for p in range(P):
+            x = torch.zeros(d, device=DEV)
+            x[:seg_host[-1]] = torch.randn(seg_host[-1], device=DEV) * 1e-2 + 1e-3
+            ops.mx8_pack(x, packed[p], d)
+        del x
+        block = torch.empty(P, d, device=DEV)
+        bufs = [torch.zeros(d, device=DEV) for _ in range(4)]
+
+        def geo_packed(packed=packed, P=P):
+            z, z_new = bufs[0].zero_(), bufs[1].zero_()
+            part = ops.mx8_weiszfeld_step(packed, torch.full((P, L), 1.0 / P, device=DEV), seg, z)
+            for it in range(n_iter):
+                part = ops.mx8_weiszfeld_step(packed, weights(part), seg, z_new, dist=it < n_iter - 1)
+                z, z_new = z_new, z
+            return z
+
+        def geo_block(packed=packed, block=block):
+            ops.mx8_unpack(packed, block)
+            z, z_new = block.mean(dim=0), bufs[2].zero_()
+            for _ in range(n_iter):
+                ops.segment_weighted_mean(block, weights(ops.segment_sqdist(block, z, seg)), seg, z_new)
+                z, z_new = z_new, z
+            return z
+
+        def clip_packed(packed=packed, P=P):
+            v = bufs[3].zero_()
+            d2 = ops.mx8_clip_step_(packed, v, torch.zeros(P, device=DEV))
+            for it in range(1, clip_iters + 1):
+                d2 = ops.mx8_clip_step_(packed, v, factors(d2, P), dist=it < clip_iters)
+            return v
+
+        def clip_block(packed=packed, block=block, P=P):
+            ops.mx8_unpack(packed, block)
+            v = bufs[2].zero_()
+            d2 = ops.clip_step_(block, v, torch.zeros(P, device=DEV))
+            for it in range(1, clip_iters + 1):
+                d2 = ops.clip_step_(block, v, factors(d2, P), dist=it < clip_iters)
+            return v
+
+        a, b = geo_packed().clone(), geo_block().clone()
+        print(f"# P={P}: geometric median, max |packed - block| / max |block| = "
+              f"{float((a - b).abs().max() / b.abs().max()):.3e}")
+        a, b = clip_packed().clone(), clip_block().clone()
+        print(f"# P={P}: centered clip, max |packed - block| / max |block| = "
+              f"{float((a - b).abs().max() / b.abs().max()):.3e}")
+        del a, b
+        arms += [(f"geometric median, packed, {n_iter + 1} passes (P={P})", geo_packed, 3),
+                 (f"geometric median, unpack + block (P={P})", geo_block, 3),
+                 (f"centered clip, packed, {clip_iters + 1} passes (P={P})", clip_packed, 10),
+                 (f"centered clip, unpack + block (P={P})", clip_block, 10)]
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn, iters in arms:
+            ms = ev_ms(fn, iters=iters, warmup=1)
+            if name not in times:
+                times[name] = []
+                order.append(name)
+            times[name].append(ms)
+            print(f"{name:52} {ms*1e3:9.1f} us")
+    print("# min - max over rounds")
+    for name in order:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:52} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -925,6 +1021,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("SIGN_ONLY") == "1":
         sign_majority_compare()
+        raise SystemExit(0)
+    if os.environ.get("MX8_ITER_ONLY") == "1":
+        mx8_iter_compare()
         raise SystemExit(0)
     if os.environ.get("MX8_GRAM_ONLY") == "1":
         mx8_gram_compare()
