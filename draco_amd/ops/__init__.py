@@ -33,6 +33,8 @@ __all__ = [
     "mx4_pack",
     "mx4_unpack",
     "mx4_chunk_bytes",
+    "mx4_column_trimmed_mean",
+    "mx4_column_mean_around",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -329,6 +331,29 @@ def mx4_unpack(packed, out):
         ext.mx4_unpack(packed, out)
         return
     fallback.mx4_unpack(packed, out)
+
+
+def mx4_column_trimmed_mean(packed, lo, hi, out):
+    """out (chunk,) fp32 = column_trimmed_mean(mx4_unpack(packed), lo, hi), bit for bit, for
+    packed (P, mx4_chunk_bytes(chunk)) uint8, 1 <= P <= 64, chunk % 64 == 0.  On the GPU one
+    kernel reads the records themselves (a dword of codes is eight columns of a lane) and the
+    fp32 block is never formed.  Definition and checks: fallback.mx4_column_trimmed_mean."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx4_column_trimmed_mean(packed, int(lo), int(hi), out)
+        return
+    fallback.mx4_column_trimmed_mean(packed, int(lo), int(hi), out)
+
+
+def mx4_column_mean_around(packed, keep, clo, chi, out):
+    """out (chunk,) fp32 = column_mean_around(mx4_unpack(packed), keep, clo, chi), bit for
+    bit; shapes and kernel as mx4_column_trimmed_mean.  Definition and checks:
+    fallback.mx4_column_mean_around."""
+    ext = _native_for(packed)
+    if ext is not None:
+        ext.mx4_column_mean_around(packed, int(keep), int(clo), int(chi), out)
+        return
+    fallback.mx4_column_mean_around(packed, int(keep), int(clo), int(chi), out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

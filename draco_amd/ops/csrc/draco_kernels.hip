@@ -2127,9 +2127,11 @@ k_mx8_col(const unsigned char *__restrict__ packed, int P, int a, int b, int c, 
   }
 }
 
-// The checks shared by the two ops, before any launch; returns the units of the call.
-static inline int check_mx8_col(const char *op, const torch::Tensor &packed,
-                                const torch::Tensor &out) {
+// The checks shared by the column ops of both block-scaled wires, before any launch; returns
+// the units (wave loads of `unit` columns) of the call.  With chunk <= 2^30 every column and
+// every byte offset inside a record fits 32 bits, the last unit's outside lanes included.
+static inline int check_mx_col(const char *op, const torch::Tensor &packed,
+                               const torch::Tensor &out, long (*chunk_bytes)(long), long unit) {
   CHECK_IN(packed);
   CHECK_IN(out);
   TORCH_CHECK(packed.device() == out.device(), op, ": tensors must be on one device");
@@ -2138,13 +2140,18 @@ static inline int check_mx8_col(const char *op, const torch::Tensor &packed,
   long chunk = out.numel();
   TORCH_CHECK(chunk % 64 == 0, op, ": chunk must be a multiple of 64, got ", chunk);
   TORCH_CHECK(chunk <= 0x40000000L, op, ": chunk ", chunk, " exceeds the 32-bit column offset");
-  TORCH_CHECK(packed.dim() == 2 && packed.size(1) == mx8_chunk_bytes(chunk), op,
-              ": packed must be (P, ", mx8_chunk_bytes(chunk), ") for chunk ", chunk);
+  TORCH_CHECK(packed.dim() == 2 && packed.size(1) == chunk_bytes(chunk), op,
+              ": packed must be (P, ", chunk_bytes(chunk), ") for chunk ", chunk);
   long P = packed.size(0);
   TORCH_CHECK(P >= 1 && P <= 64, op, " kernel supports 1 <= P <= 64, got ", P);
   TORCH_CHECK((uintptr_t)packed.data_ptr() % 16 == 0 && (uintptr_t)out.data_ptr() % 16 == 0, op,
               ": tensors must be 16-byte aligned");
-  return (int)((chunk + 255) / 256);
+  return (int)((chunk + unit - 1) / unit);
+}
+
+static inline int check_mx8_col(const char *op, const torch::Tensor &packed,
+                                const torch::Tensor &out) {
+  return check_mx_col(op, packed, out, mx8_chunk_bytes, 256);
 }
 
 template <bool AROUND>
@@ -3183,6 +3190,170 @@ void mx4_unpack(torch::Tensor packed, torch::Tensor out) {
          chunk, mx4_chunk_bytes(chunk), upr, units);
 }
 
+// --------------------------------------------------------------------------- mx4 column rules
+// mx4_column_trimmed_mean / mx4_column_mean_around: mx4_unpack followed by
+// column_trimmed_mean / column_mean_around, bit for bit, in one launch that reads the packed
+// records themselves: ~0.53 B per row and column instead of 0.53 B + 4 B written + 4 B read
+// back, and no (P, chunk) fp32 block anywhere.  The sort and the rule arithmetic are
+// k_mx8_col's (sort_columns, trimmed_sorted, mean_around_sorted, unchanged); the record is
+// not: two codes per byte, no NaN code, a scale clamp of 2.
+//
+// Work split.  A wave walks units of 512 consecutive columns, k_mx4_pack's unit (grid-stride
+// over units, one unit per wave per trip); a lane owns the EIGHT adjacent columns 8*lane ..
+// 8*lane+7 and per row loads one dword of codes, 256 contiguous bytes per wave.  Eight
+// aligned columns lie in one 32-element block, so one scale byte per row serves them; it is a
+// per-lane byte load (four lanes read the same byte, 16 contiguous bytes per wave and row).
+// The row base is wave-uniform and the lane offsets 32-bit (checked on the host).  All P code
+// loads and all P scale loads of a unit are issued before the first conversion, behind
+// wave-uniform `p < P` tests.  chunk % 64 == 0, so a lane's eight columns are inside the
+// record or outside as a whole: no cross-lane step, no LDS, no atomics, and an outside lane
+// of the unit that ends the shard simply skips.
+//
+// Registers.  The codes stay packed, N dwords.  A row's scale byte becomes the fp32 operand
+// 2^(max(s,2)-127): a register per row, or its exponent alone, four to a register, for the
+// padded sizes at which one sorted column is all that fits beside the codes (mx4_cols).
+// E2M1 has no NaN code, so a NaN block (s = 0xFF) cannot be folded into the codes as a NaN,
+// which is what k_mx8_col does.  It is folded in as what the fp32 column op turns a NaN
+// into before it sorts, +inf: the row's dword becomes eight codes 7 (0x77777777) and its
+// scale operand 2^127, and 6 * 2^127 overflows to +inf in the convert, the same overflow an
+// honest code 7 at s = 254 takes.  All eight of a lane's columns share the block, so the
+// whole dword goes; a padding row (p >= P) starts as such a row.  The conversion loop then
+// has no NaN test and no select at all.  (A 64-bit row mask per lane with a select per
+// value was built first: the compiler kept the N mask tests as N lane masks in SGPR pairs,
+// spilled to VGPR lanes, at 130 / 169 VGPRs for N = 24 / 32 trimmed mean against 112 / 144
+// here, one wave per SIMD fewer at each.)  The scale operand is never a NaN.
+//
+// Conversion loop.  v_cvt_scalef32_pk_f32_fp4 of byte 0 yields two columns, the low nibble
+// then the high one; its byte select is an immediate, so the loop over a lane's columns is
+// NOT unrolled: it always converts byte 0 and shifts the codes down by 8 bits, so one copy
+// of the sort network serves all eight columns.  Where two sorted columns do not fit
+// (COLS = 1) the codes shift by 4 bits and .x alone is taken.  The results rotate through two
+// float4 (no run-time-indexed array) and leave as two 16-byte stores per lane; the output is
+// 1/P of the traffic, so k_mx4_unpack's store layout is not worth a lane shuffle here.
+//
+// Relied on from the convert: what k_mx4_unpack relies on and the header of the mx4 wire
+// records as measured (every code byte exact at every scale operand 2^-125 .. 2^127, -0.0
+// and the overflow of code 7 at s = 254 to +-Inf included, which is also what makes a NaN
+// block +inf here; +-Inf sort as themselves, as they do after mx4_unpack).  Not relied on: a NaN or subnormal scale operand (never issued), and
+// bytes 1..3 of the source (shifted into byte 0 instead of selected).  s[] is indexed by
+// compile-time constants only; no instantiation uses scratch
+// (profiles/kernel_bw_mx4_fused.txt).
+template <int N> constexpr int mx4_cols = N <= 32 ? 2 : 1;
+
+// AROUND: (a, b, c) = (keep, clo, chi), (f, g) = (ccnt, kcnt); else (a, b) = (lo, hi), f = cnt
+template <int N, int COLS, bool AROUND>
+__global__ void __launch_bounds__(NTHREADS) NO_PACKED_FP32
+k_mx4_col(const unsigned char *__restrict__ packed, int P, int a, int b, int c, float f, float g,
+          float4 *__restrict__ out, unsigned chunk, long cbytes, int units) {
+  const int lane = threadIdx.x % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const int ustride = gridDim.x * (NTHREADS / WAVE);
+  constexpr bool PACK = COLS == 1;  // scale exponents four to a register
+  for (int u = blockIdx.x * (NTHREADS / WAVE) + wave; u < units; u += ustride) {
+    const unsigned o = (unsigned)u * 512u + 8u * lane;  // the lane's first column
+    if (o >= chunk) continue;
+    const unsigned co = o / 2, so = chunk / 2 + o / 32;  // its code dword, its block's scale byte
+    unsigned codes[N], sb[N];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      codes[p] = 0u;
+      sb[p] = 0xffu;  // a padding row is a NaN block
+      if (p < P) {
+        const unsigned char *rec = packed + p * cbytes;
+        codes[p] = *reinterpret_cast<const unsigned *>(rec + co);
+        sb[p] = rec[so];
+      }
+    }
+    unsigned sc[PACK ? N / 4 : N] = {};
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      bool nan_block = sb[p] == 0xffu;
+      codes[p] = nan_block ? 0x77777777u : codes[p];  // 6 * 2^127 = +inf, eight times
+      unsigned e = nan_block ? 254u : max(sb[p], 2u);
+      if constexpr (PACK) sc[p / 4] |= e << (8 * (p % 4));
+      else sc[p] = e << 23;
+    }
+    float4 y0 = make_float4(0.f, 0.f, 0.f, 0.f), y1 = y0;
+#pragma unroll 1
+    for (int k = 0; k < 8 / COLS; ++k) {
+      float s[COLS][N];
+      if constexpr (PACK) {
+        // as in k_mx8_col: keeps the compiler from hoisting the N unpacked scales out of
+        // the loop, back into N registers
+#pragma unroll
+        for (int p = 0; p < N / 4; ++p) asm volatile("" : "+v"(sc[p]));
+      }
+#pragma unroll
+      for (int p = 0; p < N; ++p) {
+        unsigned scale = PACK ? (sc[p / 4] >> (8 * (p % 4)) & 0xffu) << 23 : sc[p];
+        // ... and from issuing all N converts first, each holding a register pair for the
+        // one value that is taken: a convert waits for the one before it
+        if (PACK && p > 0) asm volatile("" : "+v"(s[0][p - 1]), "+v"(codes[p]));
+        mx8_v2f v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes[p], __uint_as_float(scale), 0);
+        codes[p] >>= 4 * COLS;
+        s[0][p] = v.x;
+        if constexpr (COLS == 2) s[1][p] = v.y;
+      }
+      float r[COLS];
+#pragma unroll
+      for (int q = 0; q < COLS; ++q) {
+        sort_columns(s[q], std::make_integer_sequence<int, kMergeExchange<N>.n>{});
+        r[q] = AROUND ? mean_around_sorted(s[q], P, a, b, c, f, g) : trimmed_sorted(s[q], a, b, f);
+      }
+      // the results move down COLS places per trip: after the last one y0 holds columns
+      // 0..3 and y1 columns 4..7
+      if constexpr (COLS == 2) {
+        y0 = make_float4(y0.z, y0.w, y1.x, y1.y);
+        y1 = make_float4(y1.z, y1.w, r[0], r[1]);
+      } else {
+        y0 = make_float4(y0.y, y0.z, y0.w, y1.x);
+        y1 = make_float4(y1.y, y1.z, y1.w, r[0]);
+      }
+    }
+    out[o / 4] = y0;
+    out[o / 4 + 1] = y1;
+  }
+}
+
+static inline int check_mx4_col(const char *op, const torch::Tensor &packed,
+                                const torch::Tensor &out) {
+  return check_mx_col(op, packed, out, mx4_chunk_bytes, 512);
+}
+
+template <bool AROUND>
+static inline void launch_mx4_col(const torch::Tensor &packed, const torch::Tensor &out, int units,
+                                  int a, int b, int c, float f, float g) {
+  if (units == 0) return;  // chunk = 0: no launch
+  long P = packed.size(0), chunk = out.numel();
+  dim3 grid(n_blocks(units, NTHREADS / WAVE));
+  for_padded(P, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    launch(k_mx4_col<N, mx4_cols<N>, AROUND>, grid, 0, packed.data_ptr<uint8_t>(), (int)P, a, b, c,
+           f, g, (float4 *)out.data_ptr<float>(), (unsigned)chunk, mx4_chunk_bytes(chunk), units);
+  });
+}
+
+void mx4_column_trimmed_mean(torch::Tensor packed, long lo, long hi, torch::Tensor out) {
+  int units = check_mx4_col("mx4_column_trimmed_mean", packed, out);
+  long P = packed.size(0);
+  TORCH_CHECK(0 <= lo && lo < hi && hi <= P,
+              "mx4_column_trimmed_mean: need 0 <= lo < hi <= P, got lo=", lo, " hi=", hi, " P=", P);
+  launch_mx4_col<false>(packed, out, units, (int)lo, (int)hi, 0, (float)(hi - lo), 0.f);
+}
+
+void mx4_column_mean_around(torch::Tensor packed, long keep, long clo, long chi,
+                            torch::Tensor out) {
+  int units = check_mx4_col("mx4_column_mean_around", packed, out);
+  long P = packed.size(0);
+  TORCH_CHECK(1 <= keep && keep <= P,
+              "mx4_column_mean_around: need 1 <= keep <= P, got keep=", keep, " P=", P);
+  TORCH_CHECK(0 <= clo && clo < chi && chi <= P,
+              "mx4_column_mean_around: need 0 <= clo < chi <= P, got clo=", clo, " chi=", chi,
+              " P=", P);
+  launch_mx4_col<true>(packed, out, units, (int)keep, (int)clo, (int)chi, (float)(chi - clo),
+                       (float)keep);
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -3225,4 +3396,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx8_segment_mean_around", &mx8_segment_mean_around);
   m.def("mx4_pack", &mx4_pack);
   m.def("mx4_unpack", &mx4_unpack);
+  m.def("mx4_column_trimmed_mean", &mx4_column_trimmed_mean);
+  m.def("mx4_column_mean_around", &mx4_column_mean_around);
 }

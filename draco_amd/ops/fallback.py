@@ -840,20 +840,21 @@ def column_mean_around(x: torch.Tensor, keep: int, clo: int, chi: int,
 
 
 # --------------------------------------------------------------------- mx8 column rules
-def _mx8_decoded(op: str, packed: torch.Tensor, out: torch.Tensor):
-    """The checks of the two ops below and the decoded (P, chunk) block.  The format is
-    mx8_unpack's: it has no second statement here."""
+def _mx8_decoded(op: str, packed: torch.Tensor, out: torch.Tensor, chunk_bytes=mx8_chunk_bytes,
+                 unpack=mx8_unpack):
+    """The checks of the ops below and the decoded (P, chunk) block.  The format is
+    mx8_unpack's (mx4_unpack's for the mx4 ops): it has no second statement here."""
     if out.dtype != torch.float32:
         raise ValueError(f"{op}: out must be fp32, got {out.dtype}")
     if not out.is_contiguous():
         raise ValueError(f"{op}: out must be contiguous")
     chunk = out.numel()
-    if packed.dim() != 2 or packed.shape[1] != mx8_chunk_bytes(chunk):
-        raise ValueError(f"{op}: packed must be (P, {mx8_chunk_bytes(chunk)}) for chunk {chunk}")
+    if packed.dim() != 2 or packed.shape[1] != chunk_bytes(chunk):
+        raise ValueError(f"{op}: packed must be (P, {chunk_bytes(chunk)}) for chunk {chunk}")
     if not 1 <= packed.shape[0] <= 64:
         raise ValueError(f"{op} supports 1 <= P <= 64, got {packed.shape[0]}")
     x = torch.empty(packed.shape[0], chunk, dtype=torch.float32, device=out.device)
-    mx8_unpack(packed, x)  # dtype, device, contiguity of packed, chunk % 64
+    unpack(packed, x)  # dtype, device, contiguity of packed, chunk % 64
     return x
 
 
@@ -872,6 +873,25 @@ def mx8_column_mean_around(packed: torch.Tensor, keep: int, clo: int, chi: int,
     """out (chunk,) = column_mean_around of the decoded rows of packed; as
     mx8_column_trimmed_mean."""
     x = _mx8_decoded("mx8_column_mean_around", packed, out)
+    column_mean_around(x, keep, clo, chi, out.view(-1))
+
+
+# --------------------------------------------------------------------- mx4 column rules
+@torch.no_grad()
+def mx4_column_trimmed_mean(packed: torch.Tensor, lo: int, hi: int, out: torch.Tensor) -> None:
+    """out (chunk,) = column_trimmed_mean of the decoded rows of packed (P,
+    mx4_chunk_bytes(chunk)) uint8, 1 <= P <= 64: by definition mx4_unpack into a temporary,
+    then column_trimmed_mean.  The HIP kernel gives the same bits from the packed bytes."""
+    x = _mx8_decoded("mx4_column_trimmed_mean", packed, out, mx4_chunk_bytes, mx4_unpack)
+    column_trimmed_mean(x, lo, hi, out.view(-1))
+
+
+@torch.no_grad()
+def mx4_column_mean_around(packed: torch.Tensor, keep: int, clo: int, chi: int,
+                           out: torch.Tensor) -> None:
+    """out (chunk,) = column_mean_around of the decoded rows of packed; as
+    mx4_column_trimmed_mean."""
+    x = _mx8_decoded("mx4_column_mean_around", packed, out, mx4_chunk_bytes, mx4_unpack)
     column_mean_around(x, keep, clo, chi, out.view(-1))
 
 

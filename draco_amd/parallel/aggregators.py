@@ -88,10 +88,13 @@ class Aggregator:
     # stays non-finite.  With one rank the rows are still packed and unpacked.  The
     # bucketed path is not built for this wire: the row ships whole from aggregate().
     # "mx4" (--compress-grad mx4) takes the same route with ops.mx4_pack / ops.mx4_unpack: one
-    # E2M1 nibble per element (7.5x fewer all_to_all bytes than fp32), always through the
-    # decoded block (no rule kernel reads mx4 records; exchanged_packed stays None).  With
-    # wire_seed set (--mx-rounding stochastic) every packed row is rounded stochastically
-    # under its own seed (_row_seed).
+    # E2M1 nibble per element (7.5x fewer all_to_all bytes than fp32).  The per-coordinate
+    # rules with no collusion and no mixing read the mx4 records in their kernel
+    # (ops.mx4_column_trimmed_mean / ops.mx4_column_mean_around), asking exchanged_packed for
+    # both wires; every other rule reads the decoded block (exchanged_packed's default is the
+    # mx8 wire alone, their kernels read mx8 records only).  With wire_seed set
+    # (--mx-rounding stochastic) every packed row is rounded stochastically under its own
+    # seed (_row_seed).
     wire = None
     wire_seed = None  # cfg.seed for stochastic rounding on the mx4 wire; None: nearest
 
@@ -210,14 +213,15 @@ class Aggregator:
             self.mixing(recv)
         return recv
 
-    def exchanged_packed(self, payload: torch.Tensor):
-        """On the mx8 wire with no collusion and no mixing attached: the drained exchange
+    def exchanged_packed(self, payload: torch.Tensor, wires=("mx8",)):
+        """On one of `wires` with no collusion and no mixing attached: the drained exchange
         as it travelled, (rows*world, chunk_bytes) uint8 in exchanged()'s row order, for the
         rules whose kernel decodes it itself (ops.mx8_column_trimmed_mean /
         ops.mx8_column_mean_around, ops.mx8_segment_gram / ops.mx8_segment_mean_around,
         ops.mx8_weiszfeld_step, ops.mx8_clip_step_); the fp32 block is then never allocated.  None
-        otherwise (nothing is exchanged yet): the caller goes on to exchanged()."""
-        if self.wire != "mx8" or self.collusion is not None or self.mixing is not None:
+        otherwise (nothing is exchanged yet): the caller goes on to exchanged().  The two
+        column rules pass wires=_COLUMN_OPS, which has the mx4 wire as well."""
+        if self.wire not in wires or self.collusion is not None or self.mixing is not None:
             return None
         self._start_rest(payload)
         self._drain()
@@ -287,6 +291,12 @@ _PACKED_WIRES = {
     "mx8": (lambda g, out, chunk, seed: ops.mx8_pack(g, out, chunk), ops.mx8_unpack,
             ops.mx8_chunk_bytes),
     "mx4": (ops.mx4_pack, ops.mx4_unpack, ops.mx4_chunk_bytes),
+}
+
+# wire -> (column_trimmed_mean, column_mean_around) on that wire's packed records
+_COLUMN_OPS = {
+    "mx8": (ops.mx8_column_trimmed_mean, ops.mx8_column_mean_around),
+    "mx4": (ops.mx4_column_trimmed_mean, ops.mx4_column_mean_around),
 }
 
 
@@ -865,10 +875,10 @@ class TrimmedMeanAggregator(Aggregator):
         return self.trim, P - self.trim
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
-        packed = self.exchanged_packed(payload)  # (P, chunk_bytes), or None
+        packed = self.exchanged_packed(payload, wires=_COLUMN_OPS)  # (P, chunk_bytes), or None
         if packed is not None:
             lo, hi = self._bounds(packed.shape[0])
-            ops.mx8_column_trimmed_mean(packed, lo, hi, self._shard_out)
+            _COLUMN_OPS[self.wire][0](packed, lo, hi, self._shard_out)
         else:
             recv = self.exchanged(payload)  # (P, shard)
             lo, hi = self._bounds(recv.shape[0])
@@ -926,10 +936,10 @@ class MeanAroundAggregator(Aggregator):
         return P - self.b, self.b, P - self.b
 
     def aggregate(self, payload: torch.Tensor, step: int) -> torch.Tensor:
-        packed = self.exchanged_packed(payload)  # (P, chunk_bytes), or None
+        packed = self.exchanged_packed(payload, wires=_COLUMN_OPS)  # (P, chunk_bytes), or None
         if packed is not None:
             keep, clo, chi = self._bounds(packed.shape[0])
-            ops.mx8_column_mean_around(packed, keep, clo, chi, self._shard_out)
+            _COLUMN_OPS[self.wire][1](packed, keep, clo, chi, self._shard_out)
         else:
             recv = self.exchanged(payload)  # (P, shard)
             keep, clo, chi = self._bounds(recv.shape[0])

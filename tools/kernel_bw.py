@@ -664,7 +664,7 @@ def mx4_compare(rounds=3):
         print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
 
 
-def mx8_fused_compare(rounds=3):
+def mx8_fused_compare(rounds=3, wire="mx8"):
     """The rules that decode the MXFP8 records in their own kernel (ops.mx8_column_trimmed_mean
     / ops.mx8_column_mean_around) beside the two-launch route they replace (mx8_unpack into a
     (P, d) fp32 block, then the fp32 column op), on packed 24 x 11.2M and 64 x 11.2M blocks of
@@ -674,28 +674,31 @@ def mx8_fused_compare(rounds=3):
     comparison.  Outputs are compared once before timing (NaN as NaN, values ==); event
     timing, the arms alternate inside each round; min-max over the rounds per arm."""
     d = (11_173_952 + 63) // 64 * 64
-    cb = ops.mx8_chunk_bytes(d)
+    pack, unpack = getattr(ops, wire + "_pack"), getattr(ops, wire + "_unpack")
+    col_tm = getattr(ops, wire + "_column_trimmed_mean")
+    col_ma = getattr(ops, wire + "_column_mean_around")
+    cb = getattr(ops, wire + "_chunk_bytes")(d)
     times, order = {}, []
     for P in (24, 64):
         packed = torch.empty(P, cb, dtype=torch.uint8, device=DEV)
         for p in range(P):
             x = torch.randn(d, device=DEV) * 1e-2
             x[p::1001] = float("nan")
-            ops.mx8_pack(x, packed[p], d)
+            pack(x, packed[p], d)
         del x
         block = torch.empty(P, d, device=DEV)
         out, ref = torch.empty(d, device=DEV), torch.empty(d, device=DEV)
         med = ((P - 1) // 2, P // 2 + 1)
-        rules = [("trimmed mean b=1", ops.mx8_column_trimmed_mean, ops.column_trimmed_mean, (1, P - 1)),
-                 ("median", ops.mx8_column_trimmed_mean, ops.column_trimmed_mean, med),
-                 ("meamed b=1", ops.mx8_column_mean_around, ops.column_mean_around, (P - 1, *med))]
-        arms = [(f"mx8_unpack ({P} x 11.2M)", lambda: ops.mx8_unpack(packed, block), P * (cb + 4 * d))]
+        rules = [("trimmed mean b=1", col_tm, ops.column_trimmed_mean, (1, P - 1)),
+                 ("median", col_tm, ops.column_trimmed_mean, med),
+                 ("meamed b=1", col_ma, ops.column_mean_around, (P - 1, *med))]
+        arms = [(f"{wire}_unpack ({P} x 11.2M)", lambda: unpack(packed, block), P * (cb + 4 * d))]
         for name, fused, plain, args in rules:
             def one(fused=fused, args=args):
                 fused(packed, *args, out)
 
             def two(plain=plain, args=args):
-                ops.mx8_unpack(packed, block)
+                unpack(packed, block)
                 plain(block, *args, ref)
             one(), two()
             nan = torch.isnan(ref)
@@ -716,6 +719,17 @@ def mx8_fused_compare(rounds=3):
     for name, nbytes in order:
         lo, hi = min(times[name]), max(times[name])
         print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
+
+
+def mx4_fused_compare(rounds=3):
+    """mx8_fused_compare on the MXFP4 wire: ops.mx4_column_trimmed_mean /
+    ops.mx4_column_mean_around on the packed records beside the two-launch route they replace
+    (mx4_unpack into a (P, d) fp32 block, then the fp32 column op), on packed 24 x 11.2M and
+    64 x 11.2M blocks of distinct rows, rounded to nearest: trimmed mean b=1, median, meamed
+    b=1; mx4_unpack alone is the floor of the two-launch route.  Each arm's GB/s counts its own
+    bytes; the time is the comparison.  Outputs are compared once before timing (NaN as NaN,
+    values ==); event timing, the arms alternate inside each round; min-max over the rounds."""
+    mx8_fused_compare(rounds, wire="mx4")
 
 
 def mx8_gram_compare(rounds=3):
@@ -1030,6 +1044,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if os.environ.get("MX8_FUSED_ONLY") == "1":
         mx8_fused_compare()
+        raise SystemExit(0)
+    if os.environ.get("MX4_FUSED_ONLY") == "1":
+        mx4_fused_compare()
         raise SystemExit(0)
     if os.environ.get("MX4_ONLY") == "1":
         mx4_compare()
