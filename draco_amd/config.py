@@ -88,6 +88,10 @@ class Config:
     compile: bool = False         # torch.compile the model before hipGraph capture
     fused_norm: bool = True       # ResNet BatchNorm+add+ReLU through the fused NHWC HIP
                                   # kernels (GPU, not under compile; ops/fused_bn.py)
+    grad_sink: bool = True        # colocated trainer: gradients reach the payload row
+                                  # through one scatter kernel and, under bf16, a per-step
+                                  # bf16 shadow of the parameters (not under compile or the
+                                  # bucketed overlap; parallel/trainer.py _setup_sink)
     data_root: str = ""           # directory with real MNIST/CIFAR files (IDX/pickle);
                                   # empty or missing files -> deterministic synthetic data
     synthetic_task: str = "means" # means | teacher (see data/synthetic.py: teacher is

@@ -35,6 +35,7 @@ __all__ = [
     "mx4_chunk_bytes",
     "mx4_column_trimmed_mean",
     "mx4_column_mean_around",
+    "scatter_grads_",
     "rows_equal",
     "pair_maxdiff",
     "row_absmax",
@@ -354,6 +355,43 @@ def mx4_column_mean_around(packed, keep, clo, chi, out):
         ext.mx4_column_mean_around(packed, int(keep), int(clo), int(chi), out)
         return
     fallback.mx4_column_mean_around(packed, int(keep), int(clo), int(chi), out)
+
+
+def scatter_grads_(srcs, offsets, out, channels_last=False):
+    """The gradient sink: out[o_i : o_i + n_i] = float(src_i) for the fp32 / bf16 tensors
+    srcs at the host offsets, in the order of the flat space (NHWC for 4-D tensors when
+    channels_last), and +0.0 everywhere else in the (d_pad,) fp32 row out, the pad tail
+    included: every element is written exactly once and the caller clears nothing.  On the
+    GPU one kernel (k_scatter_grads) whose tensor table travels by value in its arguments,
+    64 ranges per launch: no device table, no copy, no synchronisation, so the call can be
+    captured into a graph.  The kernel reads a source in storage order; a source that is
+    not dense in the flat order (contiguous, or channels-last-contiguous for 4-D when
+    channels_last) is written by a strided copy_ into its range instead.  Definition and
+    checks: fallback.scatter_grads_."""
+    ext = _native_for(out)
+    if ext is None:
+        fallback.scatter_grads_(srcs, offsets, out, channels_last)
+        return
+    fallback.check_scatter_grads(srcs, offsets, out)
+    dense, dense_off, skip_off, skip_len = [], [], [], []
+    for s, o in zip(srcs, offsets):
+        o = int(o)
+        cl = channels_last and s.dim() == 4
+        if s.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format):
+            dense.append(s)
+            dense_off.append(o)
+            continue
+        dst = out[o : o + s.numel()]
+        if cl:
+            n, c, h, w = s.shape
+            dst = dst.view(n, h, w, c).permute(0, 3, 1, 2)
+        else:
+            dst = dst.view(s.shape)
+        with torch.no_grad():
+            dst.copy_(s)
+        skip_off.append(o)
+        skip_len.append(s.numel())
+    ext.scatter_grads(dense, dense_off, skip_off, skip_len, out)
 
 
 def rows_equal(x, a_idx, b_idx, atol):

@@ -25,6 +25,8 @@
 // geometric median) on it: codes packed in registers, each row decoded twice per pass.
 // k_mx4_pack / k_mx4_unpack (the MXFP4 4-bit wire) use the scaled FP4 converts; a block is
 // one quad of lanes, and the stochastic rounding is integer VALU work on a stateless hash.
+// k_scatter_grads (the gradient sink) writes one backward's gradient tensors into the flat
+// payload row in one pass; its tensor table travels by value in the kernel arguments.
 //
 // Build: hipcc --offload-arch=gfx950 (tools/build_ext.py); loaded as torch extension
 // draco_amd._hip_ops.  No CUDA path, no hipify — HIP-native source.
@@ -34,7 +36,9 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #define WAVE 64
 #define NTHREADS 256
@@ -3354,6 +3358,190 @@ void mx4_column_mean_around(torch::Tensor packed, long keep, long clo, long chi,
                        (float)keep);
 }
 
+// --------------------------------------------------------------------------- gradient sink
+// scatter_grads: the gradients of one backward (a list of dense fp32 / bf16 tensors) into
+// the worker's flat fp32 payload row, every element of the row written exactly once: the
+// range of source i becomes float(src_i) in the order of its storage, everything else
+// (gaps, the pad tail) becomes +0.0.  It replaces the row's memset, autograd's per-tensor
+// cast of a bf16 gradient to a new fp32 tensor and the per-parameter `grad += g` into the
+// zeroed row: one pass, the sources read once and the row written once.
+//
+// The call sits inside a captured graph, so nothing about the list may live in device
+// memory that the host writes: pointers, offsets, lengths and dtypes travel BY VALUE in
+// the kernel arguments, SINK_CAP ranges per launch (ResNet-18: 62 tensors + the tail, one
+// launch).  A block takes one SINK_CHUNK-element chunk of one range and finds it by a
+// binary search over the prefix of chunk counts in the same arguments.  Accesses are
+// 16 bytes wide wherever the destination offset and the source pointer allow: the head up
+// to the destination's first 16-byte boundary and the tail are scalar, and a source that
+// is not 16-byte aligned at that boundary is read element by element (the stores stay
+// 16 bytes).  bf16 -> fp32 is the exact widening (a 16-bit shift): NaN payloads, +-Inf,
+// -0.0 and subnormals are kept.  Definition: fallback.scatter_grads_.
+#define SINK_CAP 64
+#define SINK_CHUNK 4096
+
+struct SinkTable {
+  const void *src[SINK_CAP];  // nullptr: the range is zero-filled
+  long off[SINK_CAP];         // first destination element
+  long len[SINK_CAP];         // elements
+  int first[SINK_CAP + 1];    // first[e] = chunks of the ranges before e; first[n] = grid size
+  unsigned long bf16;         // bit e: source e is bf16 (else fp32)
+  int n;
+};
+
+__device__ __forceinline__ float sink_cvt(float v) { return v; }
+__device__ __forceinline__ float sink_cvt(unsigned short h) {
+  return __uint_as_float((unsigned)h << 16);
+}
+
+// 16 bytes of source -> 16 / sizeof(T) floats
+__device__ __forceinline__ void sink_vec(float4 *dst, const float *src, bool aligned) {
+  if (aligned) {
+    dst[0] = *(const float4 *)src;
+  } else {
+    dst[0] = make_float4(src[0], src[1], src[2], src[3]);
+  }
+}
+__device__ __forceinline__ void sink_vec(float4 *dst, const unsigned short *src, bool aligned) {
+  unsigned short h[8];
+  if (aligned) {
+    uint4 v = *(const uint4 *)src;
+    unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      h[2 * k] = (unsigned short)(w[k] & 0xffffu);
+      h[2 * k + 1] = (unsigned short)(w[k] >> 16);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) h[k] = src[k];
+  }
+  dst[0] = make_float4(sink_cvt(h[0]), sink_cvt(h[1]), sink_cvt(h[2]), sink_cvt(h[3]));
+  dst[1] = make_float4(sink_cvt(h[4]), sink_cvt(h[5]), sink_cvt(h[6]), sink_cvt(h[7]));
+}
+
+// Elements [start, end) of one range: dst and src point at the range's element 0.  T is
+// float or unsigned short (bf16 bits); src == nullptr zero-fills.
+template <typename T>
+__device__ __forceinline__ void sink_chunk(float *__restrict__ dst, const T *__restrict__ src,
+                                           long start, long end) {
+  constexpr int V = 16 / sizeof(T);  // elements per 16-byte load: 4 or 8 (whole float4 stores)
+  // head: up to the destination's first 16-byte boundary at or after `start`
+  long head = start + (long)((4 - (((uintptr_t)(dst + start) >> 2) & 3)) & 3);
+  if (head > end) head = end;
+  long nvec = (end - head) / V;
+  long tail = head + nvec * V;
+  if (src == nullptr) {
+    for (long i = start + threadIdx.x; i < head; i += NTHREADS) dst[i] = 0.f;
+    float4 *d4 = (float4 *)(dst + head);
+    for (long v = threadIdx.x; v < nvec * (V / 4); v += NTHREADS) d4[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long i = tail + threadIdx.x; i < end; i += NTHREADS) dst[i] = 0.f;
+    return;
+  }
+  for (long i = start + threadIdx.x; i < head; i += NTHREADS) dst[i] = sink_cvt(src[i]);
+  bool aligned = ((uintptr_t)(src + head) & 15) == 0;  // the same for every lane of the block
+  for (long v = threadIdx.x; v < nvec; v += NTHREADS)
+    sink_vec((float4 *)(dst + head + v * V), src + head + v * V, aligned);
+  for (long i = tail + threadIdx.x; i < end; i += NTHREADS) dst[i] = sink_cvt(src[i]);
+}
+
+__global__ void __launch_bounds__(NTHREADS)
+k_scatter_grads(float *__restrict__ out, const SinkTable t) {
+  // the range e with first[e] <= blockIdx.x < first[e + 1] (ranges are never empty)
+  int b = (int)blockIdx.x;
+  int lo = 0, hi = t.n - 1;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) >> 1;
+    if (t.first[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  long start = (long)(b - t.first[lo]) * SINK_CHUNK;
+  long len = t.len[lo];
+  long end = start + SINK_CHUNK < len ? start + SINK_CHUNK : len;
+  float *dst = out + t.off[lo];
+  if ((t.bf16 >> lo) & 1ul) sink_chunk(dst, (const unsigned short *)t.src[lo], start, end);
+  else sink_chunk(dst, (const float *)t.src[lo], start, end);
+}
+
+// srcs[i] -> out[offsets[i] : offsets[i] + srcs[i].numel()).  The ranges [skip_off[j],
+// skip_off[j] + skip_len[j]) are the caller's: it writes them itself (a source that is not
+// dense in the flat order goes through a strided copy there), so they are neither written
+// nor zeroed here.  Everything outside both lists becomes +0.0.
+void scatter_grads(std::vector<torch::Tensor> srcs, std::vector<int64_t> offsets,
+                   std::vector<int64_t> skip_off, std::vector<int64_t> skip_len,
+                   torch::Tensor out) {
+  CHECK_IN(out);
+  TORCH_CHECK(out.scalar_type() == torch::kFloat32 && out.dim() == 1,
+              "scatter_grads: out must be a 1-D fp32 row");
+  TORCH_CHECK(srcs.size() == offsets.size(), "scatter_grads: ", srcs.size(), " sources, ",
+              offsets.size(), " offsets");
+  TORCH_CHECK(skip_off.size() == skip_len.size(), "scatter_grads: skip lists differ in length");
+  long d = out.numel();
+  if (d == 0) {
+    TORCH_CHECK(srcs.empty() && skip_off.empty(), "scatter_grads: ranges beyond an empty out");
+    return;
+  }
+  float *op = out.data_ptr<float>();
+  TORCH_CHECK((uintptr_t)op % 16 == 0, "scatter_grads: out must be 16-byte aligned");
+
+  struct Range { long off, len; const void *src; bool bf16; bool skip; };
+  std::vector<Range> ranges;
+  for (size_t i = 0; i < srcs.size(); ++i) {
+    const torch::Tensor &s = srcs[i];
+    TORCH_CHECK(s.is_cuda() && s.device() == out.device(), "scatter_grads: source ", i,
+                " must be on out's device");
+    bool bf = s.scalar_type() == torch::kBFloat16;
+    TORCH_CHECK(bf || s.scalar_type() == torch::kFloat32, "scatter_grads: source ", i,
+                " must be fp32 or bf16");
+    TORCH_CHECK(s.is_non_overlapping_and_dense(), "scatter_grads: source ", i,
+                " must be dense");
+    if (s.numel() == 0) continue;
+    ranges.push_back({offsets[i], s.numel(), s.data_ptr(), bf, false});
+  }
+  for (size_t j = 0; j < skip_off.size(); ++j)
+    if (skip_len[j] != 0) ranges.push_back({skip_off[j], skip_len[j], nullptr, false, true});
+  std::sort(ranges.begin(), ranges.end(),
+            [](const Range &a, const Range &b) { return a.off < b.off; });
+  long pos = 0;
+  for (const Range &r : ranges) {
+    TORCH_CHECK(r.len > 0 && r.off >= 0 && r.off <= d && r.len <= d - r.off,
+                "scatter_grads: range [", r.off, ", ", r.off + r.len, ") beyond out's ", d,
+                " elements");
+    TORCH_CHECK(r.off >= pos, "scatter_grads: range [", r.off, ", ", r.off + r.len,
+                ") overlaps the one before it");
+    pos = r.off + r.len;
+  }
+
+  SinkTable t;
+  t.n = 0; t.bf16 = 0; t.first[0] = 0;
+  auto flush = [&]() {
+    if (t.n == 0) return;
+    launch(k_scatter_grads, dim3(t.first[t.n]), 0, op, t);
+    t.n = 0; t.bf16 = 0;
+  };
+  auto push = [&](long off, long len, const void *src, bool bf) {
+    // a range of more chunks than a grid may have blocks is split
+    const long max_len = (long)(1 << 20) * SINK_CHUNK;
+    while (len > 0) {
+      long n = len < max_len ? len : max_len;
+      if (t.n == SINK_CAP) flush();
+      int e = t.n++;
+      t.src[e] = src; t.off[e] = off; t.len[e] = n;
+      if (bf) t.bf16 |= 1ul << e;
+      t.first[e + 1] = t.first[e] + (int)((n + SINK_CHUNK - 1) / SINK_CHUNK);
+      if (src != nullptr) src = (const char *)src + n * (bf ? 2 : 4);
+      off += n; len -= n;
+      if (t.first[t.n] > (1 << 24)) flush();
+    }
+  };
+  pos = 0;
+  for (const Range &r : ranges) {
+    if (r.off > pos) push(pos, r.off - pos, nullptr, false);  // the gap before it
+    if (!r.skip) push(r.off, r.len, r.src, r.bf16);
+    pos = r.off + r.len;
+  }
+  if (pos < d) push(pos, d - pos, nullptr, false);  // the pad tail
+  flush();
+}
+
 // --------------------------------------------------------------------------- module
 void register_bn_ops(pybind11::module &m);  // bn_kernels.hip: fused BatchNorm+add+ReLU
 
@@ -3398,4 +3586,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx4_unpack", &mx4_unpack);
   m.def("mx4_column_trimmed_mean", &mx4_column_trimmed_mean);
   m.def("mx4_column_mean_around", &mx4_column_mean_around);
+  m.def("scatter_grads", &scatter_grads);
 }

@@ -1010,6 +1010,56 @@ def mx8_segment_mean_around(packed: torch.Tensor, sel: torch.Tensor, seg: torch.
     segment_mean_around(x, sel, seg, keep, clo, chi, out.view(-1))
 
 
+# --------------------------------------------------------------------- gradient sink
+def flat_order(t: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
+    """The elements of t in the order of the flat space: NHWC for a 4-D tensor of a
+    channels-last space, row-major otherwise."""
+    if channels_last and t.dim() == 4:
+        return t.permute(0, 2, 3, 1).reshape(-1)
+    return t.reshape(-1)
+
+
+def check_scatter_grads(srcs, offsets, out: torch.Tensor) -> None:
+    """The host-side checks of scatter_grads_ (the HIP op makes the same ones)."""
+    if out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous():
+        raise ValueError("scatter_grads_: out must be a contiguous 1-D fp32 row")
+    if len(srcs) != len(offsets):
+        raise ValueError(f"scatter_grads_: {len(srcs)} sources, {len(offsets)} offsets")
+    d, ranges = out.numel(), []
+    for i, (s, o) in enumerate(zip(srcs, offsets)):
+        if s.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"scatter_grads_: source {i} must be fp32 or bf16, got {s.dtype}")
+        if s.device != out.device:
+            raise ValueError(f"scatter_grads_: source {i} must be on out's device")
+        o, n = int(o), s.numel()
+        if o < 0 or o + n > d:
+            raise ValueError(f"scatter_grads_: range [{o}, {o + n}) beyond out's {d} elements")
+        if n:
+            ranges.append((o, o + n))
+    ranges.sort()
+    for (_, hi), (lo, hi2) in zip(ranges, ranges[1:]):
+        if lo < hi:
+            raise ValueError(f"scatter_grads_: range [{lo}, {hi2}) overlaps the one before it")
+
+
+@torch.no_grad()
+def scatter_grads_(srcs, offsets, out: torch.Tensor, channels_last: bool = False) -> None:
+    """The gradient sink: the gradients of one backward into a worker's flat payload row.
+
+    srcs: tensors, each fp32 or bf16, on out's device; offsets: host ints; out: (d_pad,)
+    fp32 contiguous.  out[o_i : o_i + n_i] = float(src_i), elements in the order of the
+    flat space (flat_order: NHWC for 4-D tensors when channels_last, row-major otherwise);
+    every element of out that no source covers becomes +0.0, the pad tail included.  The
+    ranges must not overlap and must lie inside out.  bf16 -> fp32 is exact (NaN, +-Inf,
+    -0.0 and subnormals are kept).  Every element of out is written; the caller clears
+    nothing.
+    """
+    check_scatter_grads(srcs, offsets, out)
+    out.zero_()
+    for s, o in zip(srcs, offsets):
+        out[int(o) : int(o) + s.numel()].copy_(flat_order(s, channels_last))
+
+
 # --------------------------------------------------------------------- dtype cast
 @torch.no_grad()
 def cast_to_bf16(x: torch.Tensor, out: torch.Tensor) -> None:

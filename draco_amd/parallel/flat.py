@@ -7,10 +7,18 @@ HBM3E the idiomatic layout is ONE contiguous fp32 buffer for all parameters and 
 
   * p.data is re-pointed at a view of the flat param buffer (zero-copy updates by the
     fused SGD/Adam kernel over one contiguous range);
-  * before each logical worker's backward, p.grad is re-pointed at views of that
-    worker's payload row, so autograd accumulates gradients directly into the comm
-    buffer — the GPU analog of the reference's interleaved per-layer isends, with no
-    packing pass at all;
+  * a logical worker's gradients reach its payload row in one of two ways.  The
+    colocated trainer's gradient sink (Config.grad_sink) takes them from
+    torch.autograd.grad and writes the whole row with one kernel
+    (ops.scatter_grads_): every element exactly once, no memset of the row, no
+    per-parameter accumulate and no .grad on the parameters; under bf16 autocast
+    the conv / linear parameters are then read from a bf16 shadow of the flat buffer
+    that is cast once per step (build_shadow / refresh_shadow), so their gradients
+    arrive as bf16 and the sink widens them.  Everywhere else (the PS topology,
+    the bucketed overlap whose hooks need AccumulateGrad, --compile) p.grad is
+    re-pointed at views of the zeroed row before the backward (attach_grads), and
+    autograd accumulates into the comm buffer directly — the GPU analog of the
+    reference's interleaved per-layer isends;
   * d is padded so every rank owns an aligned d/world shard (all_to_all / reduce
     scatter friendly) — shard alignment 64 floats = 256 B.
 
@@ -64,6 +72,9 @@ class FlatSpace:
                     self.flat_param[o : o + n].copy_(p.data.reshape(-1).to(device=device, dtype=torch.float32))
                 p.data = self._view(self.flat_param, o, n, p.shape)
 
+        self.shadow = None  # bf16 copy of flat_param, built on request (build_shadow)
+        self.shadow_leaves = {}
+
         # (L+1) segment bounds in global flat coordinates (one segment per parameter)
         self.seg_bounds = torch.tensor(self.offsets + [self.d], dtype=torch.int64)
 
@@ -89,6 +100,26 @@ class FlatSpace:
     def detach_grads(self) -> None:
         for p in self.params:
             p.grad = None
+
+    # ------------------------------------------------------------------ bf16 shadow
+    def build_shadow(self, indices) -> dict:
+        """A (d_pad,) bf16 copy of the flat parameters, and for every parameter index in
+        `indices` a view of it laid out like the parameter itself (_view: the strides
+        that `p.to(bfloat16)` has) that is a leaf with requires_grad.  Returns
+        {index: leaf}.  The buffer holds what refresh_shadow() last cast into it."""
+        self.shadow = torch.zeros(self.d_pad, dtype=torch.bfloat16, device=self.device)
+        self.shadow_leaves = {
+            i: self._view(self.shadow, self.offsets[i], self.numels[i],
+                          self.shapes[i]).detach().requires_grad_()
+            for i in indices
+        }
+        self.refresh_shadow()
+        return self.shadow_leaves
+
+    @torch.no_grad()
+    def refresh_shadow(self) -> None:
+        """shadow = bfloat16(flat_param): one pass on the current stream."""
+        self.shadow.copy_(self.flat_param)
 
     # ------------------------------------------------------------------ buckets
     def build_buckets(self, bucket_mb: float):

@@ -219,7 +219,11 @@ class Trainer:
             self._hook_adversary = False
             for i, p in enumerate(self.space.params):
                 p.register_post_accumulate_grad_hook(self._make_bucket_hook(i))
-        self.step_sync = True     # per-step device sync (bench may disable; driver
+        # gradient sink (see _setup_sink): off under --compile (dynamo traces the plain
+        # module call) and on the bucketed path, whose hooks need AccumulateGrad
+        self.use_sink = bool(cfg.grad_sink) and not cfg.compile and not self.use_buckets
+        self._setup_sink()
+        self.step_sync = True    # per-step device sync (bench may disable; driver
                                   # brackets with its own barrier+synchronize)
         self.collect_loss = True  # read losses to host each step
         self.n_fail = min(cfg.worker_fail, self.P)
@@ -327,6 +331,7 @@ class Trainer:
             _params_to_flat(self.space, tensors, new)
             setattr(self.opt, name, new)
         self._graphs = {}  # captured graphs point into the old payload/space
+        self._setup_sink()
         if self.use_buckets:
             self._hook_row = None
             self._buckets = self.space.build_buckets(self.cfg.bucket_mb)
@@ -347,20 +352,77 @@ class Trainer:
         self.comm.broadcast(meta, src=src)
         self.step_num = int(meta[0])
 
-    def _forward_backward(self, x, y, grad_row: torch.Tensor):
-        if self.use_cl and x.dim() == 4:
-            x = x.to(memory_format=torch.channels_last)
-        self.space.attach_grads(grad_row)
+    # ------------------------------------------------------------ gradient sink
+    # How a backward's gradients reach the payload row.  The plain route points p.grad at
+    # views of the row, clears the row and lets autograd accumulate: per replica and step
+    # a memset of the whole row, one `grad += g` launch per parameter, and under bf16
+    # autocast one weight cast per conv / linear in the forward plus one cast of its bf16
+    # gradient back to a new fp32 tensor in the backward — about 110 small launches and
+    # five passes over memory for a result that is one.  The sink takes the gradients
+    # from torch.autograd.grad and writes the row with ONE kernel (ops.scatter_grads_:
+    # every element exactly once, gaps and pad tail +0.0), and under autocast hands the
+    # model bf16 leaves that view a shadow of the flat parameters, cast once per step
+    # for all replicas (FlatSpace.build_shadow), so autocast has nothing to cast and the
+    # gradients arrive as bf16.  The arithmetic is the same: the rows differ from the
+    # plain route's only where that one adds -0.0 to +0.0.
+    def _setup_sink(self) -> None:
+        """Leaves of the sink for the CURRENT flat space (init, and after a rank failure
+        re-shards it)."""
+        self._sink_leaves = None
+        self._sink_swap = {}
+        if not self.use_sink:
+            return
+        params = self.space.params
+        leaves = list(params)
+        if self.autocast_dtype is not None:
+            # what autocast casts: the direct parameters of the conv and linear modules
+            # (BatchNorm's stay fp32, the fused-norm op takes them as they are)
+            cast_ids = {id(p) for m in self.model.modules()
+                        if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear))
+                        for p in m.parameters(recurse=False)}
+            idx = [i for i, p in enumerate(params) if id(p) in cast_ids]
+            # a shadow view starts 2 * offset bytes into its buffer: only a model whose
+            # cast parameters all start on 16 bytes there gets one (the casts autocast
+            # makes today are fresh, aligned allocations; LeNet's and FC's offsets are
+            # odd, and they keep the fp32 leaves and autocast's own casts)
+            if idx and all(self.space.offsets[i] % 8 == 0 for i in idx):
+                name_of = {id(p): n for n, p in self.model.named_parameters()}
+                for i, leaf in self.space.build_shadow(idx).items():
+                    leaves[i] = leaf
+                    self._sink_swap[name_of[id(params[i])]] = leaf
+        self._sink_leaves = leaves
+
+    def _backward_into(self, x, y, grad_row: torch.Tensor):
+        """The loss of (x, y), its gradient written into grad_row."""
+        if self.use_sink:
+            loss = self._loss(x, y)
+            grads = torch.autograd.grad(loss, self._sink_leaves, allow_unused=True)
+            got = [(g, o) for g, o in zip(grads, self.space.offsets) if g is not None]
+            ops.scatter_grads_([g for g, _ in got], [o for _, o in got], grad_row,
+                               channels_last=self.space.channels_last)
+            return loss
         grad_row.zero_()
         loss = self._loss(x, y)
         loss.backward()
-        return loss.detach()
+        return loss
+
+    def _forward_backward(self, x, y, grad_row: torch.Tensor):
+        if self.use_cl and x.dim() == 4:
+            x = x.to(memory_format=torch.channels_last)
+        if not self.use_sink:
+            self.space.attach_grads(grad_row)
+        return self._backward_into(x, y, grad_row).detach()
+
+    def _logits(self, x):
+        if self.use_sink:
+            return torch.func.functional_call(self.model, self._sink_swap, (x,))
+        return self.model(x)
 
     def _loss(self, x, y):
         if self.autocast_dtype is not None:
             with torch.autocast("cuda", dtype=self.autocast_dtype):
-                return self.criterion(self.model(x), y)
-        return self.criterion(self.model(x), y)
+                return self.criterion(self._logits(x), y)
+        return self.criterion(self._logits(x), y)
 
     # ------------------------------------------------------------ bucketed overlap
     def _make_bucket_hook(self, pidx: int):
@@ -521,7 +583,8 @@ class Trainer:
         return self._streams[idx]
 
     def _capture(self, grad_row: torch.Tensor, x, y):
-        self.space.attach_grads(grad_row)
+        if not self.use_sink:
+            self.space.attach_grads(grad_row)
         static_x = x.clone()
         if self.use_cl and static_x.dim() == 4:
             # capture with channels_last inputs so MIOpen sees NHWC end-to-end
@@ -530,10 +593,7 @@ class Trainer:
         static_y = y.clone()
 
         def body():
-            grad_row.zero_()
-            loss = self._loss(static_x, static_y)
-            loss.backward()
-            return loss
+            return self._backward_into(static_x, static_y, grad_row)
 
         # warm up on a side stream (MIOpen find, dynamo compile, autograd warmup)
         s = torch.cuda.Stream()
@@ -579,6 +639,11 @@ class Trainer:
         self._ev_step = self._event()
         losses = []
         adversaries = self.schedule.adversaries_at(step) if self.n_fail > 0 else frozenset()
+        if self.space.shadow is not None:
+            # the replicas' bf16 leaves: one cast per step, here and not in the optimizer
+            # kernel, because checkpoint load, failure recovery and callers write
+            # flat_param in place; the worker streams wait on this stream before a replay
+            self.space.refresh_shadow()
 
         if self.approach in ("baseline", "maj_vote"):
             pending = []

@@ -900,6 +900,63 @@ def mx8_iter_compare(rounds=3, n_iter=24, clip_iters=3):
         print(f"{name:52} {lo*1e3:9.1f} - {hi*1e3:9.1f} us")
 
 
+def grad_sink_compare(rounds=3):
+    """scatter_grads_ (the gradient sink) at the flagship shape: ResNet-18's own 62
+    gradient tensors, the 22 conv / linear ones bf16 and channels-last as the backward
+    hands them over and the 40 BatchNorm ones fp32, into one 11.2M-element fp32 row
+    (about 22 MB read + 45 MB written, one launch), beside the route it replaces on the
+    same tensors (zero_ of the row, one cast of each bf16 gradient to a new fp32 tensor,
+    one add_ per tensor into its view of the row: 85 launches) and beside combine_rows
+    with one row (one fp32 row read, one written: the streaming level for this much
+    data).  The two routes' rows are compared first (values ==); event timing, the arms
+    alternate inside each round; min-max over the rounds per arm."""
+    from draco_amd.models import build_model
+    from draco_amd.parallel.flat import FlatSpace
+    model = build_model("ResNet18", "Cifar10").to(DEV)
+    space = FlatSpace(model, 1, torch.device(DEV), channels_last=True)
+    cast = {id(p) for m in model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear))
+            for p in m.parameters(recurse=False)}
+    grads = [(torch.randn_like(p) * 1e-2).to(torch.bfloat16 if id(p) in cast else torch.float32)
+             for p in space.params]
+    assert all(g.stride() == p.stride() for g, p in zip(grads, space.params))
+    d = space.d_pad
+    row, ref = torch.full((d,), float("nan"), device=DEV), torch.empty(d, device=DEV)
+    views = [space._view(ref, o, n, s) for o, n, s in zip(space.offsets, space.numels, space.shapes)]
+    src_bytes = sum(g.numel() * g.element_size() for g in grads)
+
+    def sink():
+        ops.scatter_grads_(grads, space.offsets, row, channels_last=True)
+
+    def torch_route():
+        ref.zero_()
+        for v, g in zip(views, grads):
+            v.add_(g.float() if g.dtype != torch.float32 else g)
+
+    sink(), torch_route()
+    torch.cuda.synchronize()
+    assert bool((row == ref).all())
+    x1, idx, w = torch.randn(1, d, device=DEV), torch.zeros(1, dtype=torch.int64, device=DEV), \
+        torch.ones(1, device=DEV)
+    print(f"# d_pad = {d}, {len(grads)} tensors, {src_bytes / 1e6:.1f} MB read + {4 * d / 1e6:.1f} MB written")
+    arms = [
+        ("scatter_grads_ (62 tensors, 1 launch)", sink, src_bytes + 4 * d, dict(iters=200, warmup=20)),
+        ("zero_ + 22 casts + 62 add_", torch_route, src_bytes + 4 * d, dict(iters=50, warmup=5)),
+        ("combine_rows (1 row)", lambda: ops.combine_rows(x1, idx, w, row), 8 * d,
+         dict(iters=200, warmup=20)),
+    ]
+    times = {name: [] for name, _, _, _ in arms}
+    for r in range(rounds):
+        print(f"# round {r}")
+        for name, fn, nbytes, kw in arms:
+            ms = ev_ms(fn, **kw)
+            times[name].append(ms)
+            report(name, ms, nbytes)
+    print("# min - max over rounds, GB/s at the min (each arm counted at its MINIMUM traffic)")
+    for name, _, nbytes, _ in arms:
+        lo, hi = min(times[name]), max(times[name])
+        print(f"{name:40} {lo*1e3:9.1f} - {hi*1e3:9.1f} us  {nbytes/lo/1e6:8.1f} GB/s")
+
+
 def gram_compare():
     """Hand-written k_seg_gram vs the rocBLAS route (62 torch.mm per-segment GEMMs
     — the brief's 'plain library GEMMs belong on MFMA' case)."""
@@ -1011,6 +1068,9 @@ def fused_bn_compare(rounds=3):
 if __name__ == "__main__":
     if os.environ.get("FUSED_BN_ONLY") == "1":
         fused_bn_compare()
+        raise SystemExit(0)
+    if os.environ.get("GRAD_SINK_ONLY") == "1":
+        grad_sink_compare()
         raise SystemExit(0)
     if os.environ.get("GRAM_ONLY") == "1":
         gram_compare()
